@@ -14,6 +14,16 @@ Timing: W untimed warmup steps, then exactly K steps bracketed by
 barrier + torch.cuda.synchronize on both sides; MAX elapsed over ranks;
 rank 0 prints ONE JSON line.
 
+A plain run does only that: set up, warm up, time the K steps, print.
+``--dump-outputs DIR`` additionally writes the last timed step's loss, logits
+and a seeded sample of the updated parameters as ``DIR/<name>.npy`` (model,
+batch and dropout are seeded, so equal arguments give equal inputs and two
+builds can be compared output for output; on one MI355X two runs were
+bit-identical up to 20 steps in all and apart by up to 0.5 in the logits at
+40, see README.md). ``--full`` is where secondary
+measurements belong; there are none in this file today (sweeps, CPU and
+per-kernel figures are separate programs under ``tools/``).
+
 Baseline for ``vs_baseline``: the reference's fastest published number —
 HF Trainer fp16, 0.49 min/epoch on 2 GPUs = 312.9 samples/s (BASELINE.md,
 reference README.md:23), linearly scaled per GPU: baseline(N) = 156.46 * N.
@@ -54,7 +64,54 @@ def parse_args():
                    help="skip the 2s time-based warmup extension (for "
                         "rocprofv3 --pmc runs: counter collection "
                         "serializes kernels and the floor never finishes)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the LAST timed "
+                        "step computed as DIR/<name>.npy (float32): loss, "
+                        "logits and a seeded sample of the updated "
+                        "parameters. The time-based warmup extension does "
+                        "not train in such a run, so the last step is "
+                        "exactly step warmup+steps of the seeded start and "
+                        "two builds can be compared output for output")
+    p.add_argument("--full", action="store_true",
+                   help="also run the benchmark's secondary measurements. "
+                        "There are none today: every run is the plain "
+                        "flagship measurement (CPU baselines, sweeps and "
+                        "per-kernel figures live under tools/), so the "
+                        "flag changes nothing yet")
     return p.parse_args()
+
+
+# elements sampled per parameter tensor for --dump-outputs; ~200 tensors in
+# bert-base -> < 4 MB of float32, far below the 64 MB a dump may take
+_DUMP_PARAM_SAMPLE = 4096
+
+
+def dump_outputs(out_dir, loss, logits, model):
+    """Write the last timed step's results as float32 .npy files.
+
+    ``params_sample`` is, per parameter in ``named_parameters()`` order, the
+    elements at a fixed seeded set of flat indices (the whole tensor when it
+    is not larger than the sample), concatenated."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(4321)
+    parts = []
+    with torch.no_grad():
+        for _, p in model.named_parameters():
+            flat = p.detach().reshape(-1)
+            if flat.numel() > _DUMP_PARAM_SAMPLE:
+                idx = torch.randint(0, flat.numel(), (_DUMP_PARAM_SAMPLE,),
+                                    generator=g)
+                flat = flat[idx.to(flat.device)]
+            parts.append(flat.float().cpu())
+        arrays = {
+            "loss": loss.detach().float().reshape(1).cpu(),
+            "logits": logits.detach().float().cpu(),
+            "params_sample": torch.cat(parts),
+        }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.numpy().astype(np.float32, copy=False))
 
 
 def main():
@@ -122,7 +179,7 @@ def main():
         if scaler is not None:
             loss = scaler.scale(loss)
         loss.backward()
-        return out.loss
+        return out.loss, out.logits
 
     def opt_step(zero: bool = True):
         if isinstance(wrapped, DistributedDataParallel):
@@ -157,18 +214,18 @@ def main():
         # grad contribution in this model)
         optimizer.zero_grad(set_to_none=True)
         with torch.cuda.graph(graph):
-            static_loss = fwd_bwd()
+            static_out = fwd_bwd()
 
         def step():
             reseed_dropout()
             graph.replay()
             opt_step(zero=False)
-            return static_loss
+            return static_out
     else:
         def step():
-            loss = fwd_bwd()
+            out = fwd_bwd()
             opt_step()
-            return loss
+            return out
 
     # W contractual warmup steps, extended to >=2s of wall time so a FRESH
     # box's clock ramp-up doesn't leak into the timed region (a cold MI355X
@@ -176,6 +233,19 @@ def main():
     # Multi-rank: the extension is decided by RANK 0 and broadcast, so every
     # rank runs the SAME number of warmup steps — per-rank time-based exits
     # would mismatch the collectives inside step() and deadlock RCCL.
+    # With --dump-outputs the extension must not train: the last timed step
+    # has to be exactly step W+K of the seeded start whatever the clock says,
+    # so there it is filled with eval-mode no-grad forwards, which keep the
+    # GPU loaded but touch neither weights, optimizer nor dropout state.
+    def floor_step():
+        if not ns.dump_outputs:
+            step()
+            return
+        model.eval()
+        with torch.no_grad():
+            model(input_ids=ids, attention_mask=mask, token_type_ids=type_ids)
+        model.train()
+
     t_w = time.perf_counter()
     for _ in range(ns.warmup):
         step()
@@ -189,7 +259,7 @@ def main():
         if more == 0.0:
             break
         for _ in range(10):
-            step()
+            floor_step()
         w += 10
 
     if world > 1:
@@ -197,13 +267,17 @@ def main():
     if use_cuda:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for _ in range(ns.steps):
-        step()
+        last = step()
     if world > 1:
         dist.barrier()
     if use_cuda:
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+
+    if ns.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(ns.dump_outputs, last[0], last[1], model)
 
     if world > 1:
         t = torch.tensor([elapsed], device=device if use_cuda else "cpu",

@@ -47,6 +47,40 @@ def test_bench_json_contract_cpu():
     assert abs(r["value"] - expect) / expect < 0.05
 
 
+def test_bench_dump_outputs_reproducible_cpu(tmp_path):
+    """--dump-outputs writes the last timed step's arrays as float32 .npy;
+    equal arguments give equal inputs, so two runs agree; --full is accepted
+    and leaves the result line's meaning alone."""
+    import numpy as np
+    common = ["--model", "tiny", "--batch-size", "4", "--seq-len", "16",
+              "--steps", "3", "--warmup", "1", "--dtype", "fp32"]
+    a, b = tmp_path / "a", tmp_path / "b"
+    ra = _run_bench([*common, "--dump-outputs", str(a)])
+    rb = _run_bench([*common, "--full", "--dump-outputs", str(b)])
+    for r in (ra, rb):
+        assert r["metric"] == "samples_per_sec" and r["steps"] == 3
+        assert r["ms_per_step"] > 0 and r["dtype"] == "fp32"
+    names = sorted(p.name for p in a.iterdir())
+    assert names == ["logits.npy", "loss.npy", "params_sample.npy"]
+    assert names == sorted(p.name for p in b.iterdir())
+    total = 0
+    for n in names:
+        xa, xb = np.load(a / n), np.load(b / n)
+        assert xa.dtype == np.float32 and np.isfinite(xa).all(), n
+        np.testing.assert_array_equal(xa, xb, err_msg=n)
+        total += xa.nbytes
+    assert total <= 64 * 2**20
+    assert np.load(a / "logits.npy").shape == (4, 6)
+    assert np.load(a / "loss.npy").shape == (1,)
+
+    # a different --steps is a different last step: the dump follows it
+    c = tmp_path / "c"
+    _run_bench([*common[:-6], "--steps", "2", "--warmup", "1",
+                "--dtype", "fp32", "--dump-outputs", str(c)])
+    assert not np.array_equal(np.load(a / "params_sample.npy"),
+                              np.load(c / "params_sample.npy"))
+
+
 def test_bench_multirank_contract_cpu():
     """The driver's SCALE launch shape (torchrun, N ranks) on CPU/gloo:
     rendezvous, DDP wrap, max-over-ranks timing, ONE JSON line from rank 0

@@ -175,7 +175,7 @@ def test_zero_overflow_sync_world2():
     run_distributed(_zero_overflow_sync, world=2)
 
 
-def _zero_fp16_through_trainer(rank, world):
+def _zero_fp16_through_trainer(rank, world, out_dir):
     """The Trainer's ZeRO+scaler branch (unscale -> sync_found_inf ->
     device/sync skip -> update) end-to-end at world=2 on gloo."""
     from torch.utils.data import DataLoader
@@ -190,6 +190,10 @@ def _zero_fp16_through_trainer(rank, world):
     args.epochs = 1
     args.do_dev = False
     args.log_every = 100
+    # the end-of-training checkpoint goes to the test's tmp dir, not to the
+    # default ./output/model.pt of whatever directory pytest runs from
+    args.output_dir = out_dir
+    args.ckpt_path = out_dir + "/model.pt"
     zopt = ZeroRedundancyOptimizer(model, lr=1e-3)
     scaler = GradScaler(init_scale=8.0)
     ds = SyntheticClsDataset(16, seq_len=16, vocab_size=cfg.vocab_size)
@@ -208,5 +212,6 @@ def _zero_fp16_through_trainer(rank, world):
     assert scaler.get_scale() == 8.0
 
 
-def test_zero_fp16_through_trainer_world2():
-    run_distributed(_zero_fp16_through_trainer, world=2)
+def test_zero_fp16_through_trainer_world2(tmp_path):
+    run_distributed(_zero_fp16_through_trainer, world=2,
+                    args=(str(tmp_path),))
