@@ -166,20 +166,19 @@ class BertLayer(nn.Module):
         qkv, h_res = ops.linear_fork(h, a.qkv_weight, a.qkv_bias)
         ctx = ops.attention_packed(qkv, attn_mask, nh,
                                    cfg.attention_probs_dropout_prob, training)
-        # attention output projection + fused bias/dropout/residual/LN (K6)
+        # attention output projection + fused bias/dropout/residual/LN (K6);
+        # the bias gradient comes out of the projection's dW GEMM
         ao = self.attention.output
-        proj = ops.linear(ctx, ao.dense.weight, None)
-        h = ops.bias_dropout_residual_layernorm(
-            proj, ao.dense.bias, h_res, ao.LayerNorm.weight,
+        h = ops.linear_bias_dropout_residual_layernorm(
+            ctx, ao.dense.weight, ao.dense.bias, h_res, ao.LayerNorm.weight,
             ao.LayerNorm.bias, cfg.hidden_dropout_prob, training,
             cfg.layer_norm_eps)
         # FFN: GEMM + fused GELU (K7), GEMM + fused epilogue (K8)
         inter, h_res2 = ops.linear_fork(h, self.intermediate.dense.weight,
                                         self.intermediate.dense.bias,
                                         act="gelu")
-        down = ops.linear(inter, self.output.dense.weight, None)
-        h = ops.bias_dropout_residual_layernorm(
-            down, self.output.dense.bias, h_res2,
+        h = ops.linear_bias_dropout_residual_layernorm(
+            inter, self.output.dense.weight, self.output.dense.bias, h_res2,
             self.output.LayerNorm.weight, self.output.LayerNorm.bias,
             cfg.hidden_dropout_prob, training, cfg.layer_norm_eps)
         return h

@@ -82,6 +82,7 @@ from .functional import (  # noqa: F401,E402
     masked_softmax,
     cross_entropy,
     bias_dropout_residual_layernorm,
+    linear_bias_dropout_residual_layernorm,
     dropout,
     reseed_dropout,
     dw_stream_join,

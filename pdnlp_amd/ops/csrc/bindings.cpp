@@ -28,6 +28,7 @@ std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
 torch::Tensor gelu_bwd(torch::Tensor dy, torch::Tensor pre);
 torch::Tensor col_sum(torch::Tensor x);
 torch::Tensor gemm_tn(torch::Tensor A, torch::Tensor B);
+std::vector<torch::Tensor> gemm_tn_colsum(torch::Tensor A, torch::Tensor B);
 torch::Tensor gemm_nn(torch::Tensor A, torch::Tensor B);
 torch::Tensor gemm_nn_add(torch::Tensor A, torch::Tensor B, torch::Tensor D);
 torch::Tensor skinny_linear_fwd(torch::Tensor x, torch::Tensor w,
@@ -49,6 +50,9 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_fwd(
     torch::Tensor lnb, double p, double eps, torch::Tensor seed_buf,
     long salt);
 std::vector<torch::Tensor> bias_dropout_residual_ln_bwd(
+    torch::Tensor dout, torch::Tensor xsum, torch::Tensor mask,
+    torch::Tensor lnw, torch::Tensor mean, torch::Tensor rstd, double p);
+std::vector<torch::Tensor> bias_dropout_residual_ln_bwd_nodb(
     torch::Tensor dout, torch::Tensor xsum, torch::Tensor mask,
     torch::Tensor lnw, torch::Tensor mean, torch::Tensor rstd, double p);
 std::vector<torch::Tensor> cross_entropy_fwd(torch::Tensor logits,
@@ -89,6 +93,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gelu_bwd", &gelu_bwd);
   m.def("col_sum", &col_sum);
   m.def("gemm_tn", &gemm_tn);
+  m.def("gemm_tn_colsum", &gemm_tn_colsum);
   m.def("gemm_nn", &gemm_nn);
   m.def("gemm_nn_add", &gemm_nn_add);
   m.def("skinny_linear_fwd", &skinny_linear_fwd);
@@ -99,6 +104,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("tanh_bwd", &tanh_bwd);
   m.def("bias_dropout_residual_ln_fwd", &bias_dropout_residual_ln_fwd);
   m.def("bias_dropout_residual_ln_bwd", &bias_dropout_residual_ln_bwd);
+  m.def("bias_dropout_residual_ln_bwd_nodb",
+        &bias_dropout_residual_ln_bwd_nodb);
   m.def("cross_entropy_fwd", &cross_entropy_fwd);
   m.def("cross_entropy_bwd", &cross_entropy_bwd);
   m.def("multi_tensor_adamw", &multi_tensor_adamw);

@@ -169,7 +169,10 @@ void bdrl_bwd_dx_kernel(const T* __restrict__ dout, const T* __restrict__ xsum,
 // H threads per chunk under-fill the chip), strips folded through LDS,
 // deterministic partials [chunk][3][H] for reduce_cols_cast. grid =
 // (H/64, chunks) so both axes stay parallel.
-template <typename T>
+// DBIAS=false drops the projection-bias sum (the dy stream and the third
+// partial row): partials are [chunk][2][H]. Used when the projection's own
+// dW GEMM produces that column sum (gemm_tn_colsum).
+template <typename T, bool DBIAS = true>
 __global__ __launch_bounds__(256)
 void bdrl_bwd_dwdb_kernel(const T* __restrict__ dout,
                           const T* __restrict__ xsum,
@@ -178,7 +181,8 @@ void bdrl_bwd_dwdb_kernel(const T* __restrict__ dout,
                           const float* __restrict__ rstd,
                           float* __restrict__ part, long R, int H,
                           long rows_per_chunk) {
-  __shared__ float lds[16][3][64];
+  constexpr int KINDS = DBIAS ? 3 : 2;
+  __shared__ float lds[16][KINDS][64];
   const int quad = threadIdx.x & 15;   // 4-col group within the 64 cols
   const int strip = threadIdx.x >> 4;  // 0..15 row strips
   const int c0 = blockIdx.x * 64 + quad * 4;
@@ -190,14 +194,15 @@ void bdrl_bwd_dwdb_kernel(const T* __restrict__ dout,
       const float mu = mean[r], rs = rstd[r];
       const v4_t<T> dv = ld4(dout + r * H + c0);
       const v4_t<T> xv = ld4(xsum + r * H + c0);
-      const v4_t<T> yv = ld4(dy + r * H + c0);
+      v4_t<T> yv;
+      if constexpr (DBIAS) yv = ld4(dy + r * H + c0);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float d = elem<T>(dv, j);
         const float xh = (elem<T>(xv, j) - mu) * rs;
         dw[j] += d * xh;
         db[j] += d;
-        dbias[j] += elem<T>(yv, j);
+        if constexpr (DBIAS) dbias[j] += elem<T>(yv, j);
       }
     }
   }
@@ -205,18 +210,18 @@ void bdrl_bwd_dwdb_kernel(const T* __restrict__ dout,
   for (int j = 0; j < 4; ++j) {
     lds[strip][0][quad * 4 + j] = dw[j];
     lds[strip][1][quad * 4 + j] = db[j];
-    lds[strip][2][quad * 4 + j] = dbias[j];
+    if constexpr (DBIAS) lds[strip][2][quad * 4 + j] = dbias[j];
   }
   __syncthreads();
-  // 192 threads fold the 16 strips: thread t -> (kind = t/64, col = t%64)
-  if (threadIdx.x < 192) {
+  // KINDS*64 threads fold the 16 strips: thread t -> (kind = t/64, col = t%64)
+  if (threadIdx.x < KINDS * 64) {
     const int kind = threadIdx.x >> 6, col = threadIdx.x & 63;
     const int gc = blockIdx.x * 64 + col;
     if (gc < H) {
       float s = 0.f;
 #pragma unroll
       for (int st = 0; st < 16; ++st) s += lds[st][kind][col];
-      part[(long)blockIdx.y * 3 * H + kind * H + gc] = s;
+      part[(long)blockIdx.y * KINDS * H + kind * H + gc] = s;
     }
   }
 }
@@ -277,9 +282,15 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_fwd(
   return {out, xsum, mask, mean, rstd};
 }
 
-std::vector<torch::Tensor> bias_dropout_residual_ln_bwd(
+namespace {
+
+// shared host side of the two backward entry points; returns
+// {dy, dres, accT} with accT = [dlnw, dlnb(, dbias)] rows
+template <bool DBIAS>
+std::vector<torch::Tensor> bdrl_bwd_impl(
     torch::Tensor dout, torch::Tensor xsum, torch::Tensor mask,
     torch::Tensor lnw, torch::Tensor mean, torch::Tensor rstd, double p) {
+  constexpr int KINDS = DBIAS ? 3 : 2;
   const int H = xsum.size(-1);
   const long R = xsum.numel() / H;
   TORCH_CHECK(H % 256 == 0 && H <= 1024,
@@ -292,9 +303,9 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_bwd(
   // the strip-parallel reduce folds only 8 serial iterations per thread
   const long rows_per_chunk = (R + 31) / 32;
   const long chunks = (R + rows_per_chunk - 1) / rows_per_chunk;
-  auto part = torch::empty({chunks, 3, (long)H},
+  auto part = torch::empty({chunks, (long)KINDS, (long)H},
                            xsum.options().dtype(torch::kFloat32));
-  auto accT = torch::empty({3, (long)H}, lnw.options());
+  auto accT = torch::empty({(long)KINDS, (long)H}, lnw.options());
   const long grid = (R + 3) / 4;
   DISPATCH_FLOAT_TYPES(xsum.scalar_type(), "bdrl_bwd", [&] {
     if (drop) {
@@ -318,7 +329,7 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_bwd(
                          H, 0.f, R);
     }
     dim3 g2((H + 63) / 64, chunks);
-    hipLaunchKernelGGL((bdrl_bwd_dwdb_kernel<scalar_t>), g2, dim3(256), 0,
+    hipLaunchKernelGGL((bdrl_bwd_dwdb_kernel<scalar_t, DBIAS>), g2, dim3(256), 0,
                        stream,
                        (const scalar_t*)dout.data_ptr(),
                        (const scalar_t*)xsum.data_ptr(),
@@ -326,9 +337,26 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_bwd(
                        mean.data_ptr<float>(), rstd.data_ptr<float>(),
                        part.data_ptr<float>(), R, H, rows_per_chunk);
     hipLaunchKernelGGL((reduce_cols_cast_kernel<scalar_t>),
-                       dim3((3 * H + 63) / 64), dim3(256), 0, stream,
+                       dim3((KINDS * H + 63) / 64), dim3(256), 0, stream,
                        part.data_ptr<float>(), (scalar_t*)accT.data_ptr(),
-                       (long)(3 * H), (int)chunks);
+                       (long)(KINDS * H), (int)chunks);
   });
-  return {dy, accT[2], dres, accT[0], accT[1]};
+  return {dy, dres, accT};
+}
+
+}  // namespace
+
+std::vector<torch::Tensor> bias_dropout_residual_ln_bwd(
+    torch::Tensor dout, torch::Tensor xsum, torch::Tensor mask,
+    torch::Tensor lnw, torch::Tensor mean, torch::Tensor rstd, double p) {
+  auto r = bdrl_bwd_impl<true>(dout, xsum, mask, lnw, mean, rstd, p);
+  return {r[0], r[2][2], r[1], r[2][0], r[2][1]};
+}
+
+// backward without the projection-bias gradient: {dy, dres, dlnw, dlnb}
+std::vector<torch::Tensor> bias_dropout_residual_ln_bwd_nodb(
+    torch::Tensor dout, torch::Tensor xsum, torch::Tensor mask,
+    torch::Tensor lnw, torch::Tensor mean, torch::Tensor rstd, double p) {
+  auto r = bdrl_bwd_impl<false>(dout, xsum, mask, lnw, mean, rstd, p);
+  return {r[0], r[1], r[2][0], r[2][1]};
 }

@@ -318,8 +318,21 @@ void gemm_tn_w8_kernel(const T* __restrict__ A, const T* __restrict__ B,
 // the 8 TB/s roofline). Measured (gpurun_out/bench_dgemm*.log): the 64x64
 // single-pass kernel reached 117-381 TF on the BERT dW shapes vs
 // hipBLASLt's 169-445; this structure targets ~500 TF on all of them.
+//
+// COLSUM: the workgroups of the k0 == 0 tile column also produce the column
+// sums of A over their M span (db = sum_m dY[m, n], the bias gradient of the
+// projection whose dW this GEMM computes). sum_m A[m, n] is A^T times a
+// column of ones, i.e. one more MFMA on an a_frag that is already in
+// registers, against an all-ones B fragment: every column of that 16x16
+// result holds the row sums, so the lanes with (lane & 15) == 0 own
+// colsum[n0 + wr + i*16 + (lane>>4)*4 + r]. The four waves that share a wr
+// hold identical a_frag[0..3]; wave (wid & 3) == q takes a_frag[q], so each
+// wave issues 9 MFMAs per ms step instead of 8. The fp32 slices land behind
+// the dW partials, P[sm*N*K + split*N + n], without atomics. The dW
+// accumulators are untouched, so C is bit-identical to the plain kernel's.
 template <typename T, typename V8, bool RAWBAR = false,
-          bool NOSYNC = false>  // TIMING PROBE ONLY: numerics invalid
+          bool NOSYNC = false,  // TIMING PROBE ONLY: numerics invalid
+          bool COLSUM = false>
 __global__ __launch_bounds__(512)
 void gemm_tn_sk_kernel(const T* __restrict__ A, const T* __restrict__ B,
                        float* __restrict__ P, long M, long N, long K,
@@ -347,6 +360,13 @@ void gemm_tn_sk_kernel(const T* __restrict__ A, const T* __restrict__ B,
   const int wr = (wid >> 2) * 64, wc = (wid & 3) * 32;  // 64x32 per wave
 
   f32x4 acc[4][2] = {};
+  // wave-uniform: only the k0 == 0 tile of each n-tile row sums A
+  const bool do_cs = COLSUM && k0 == 0;
+  const int cs_q = wid & 3;
+  f32x4 cs_acc = {};
+  V8 ones;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) ones[e] = 1.0f;
 
   auto stage = [&](long m_chunk, int buf) {
 #pragma unroll
@@ -395,6 +415,35 @@ void gemm_tn_sk_kernel(const T* __restrict__ A, const T* __restrict__ B,
             frag_tr_base(lds_b[cur] + (c1 >> 6) * 8192, c1 & 63, ms * 32),
             b_frag);
       }
+      if constexpr (COLSUM) {
+        if (do_cs) {
+          // Issued BEFORE the dW MFMAs: behind them, the next ms step's
+          // LDS reads (which overwrite the fragment registers) would have
+          // to wait until this MFMA leaves the queue, i.e. for all 8 dW
+          // MFMAs to drain (measured: +12% kernel time).
+          // Wave-uniform pick through 32-bit selects: indexing a_frag by
+          // cs_q would put the fragments in scratch.
+          typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+          u32x4 sel;
+#pragma unroll
+          for (int d = 0; d < 4; ++d) {
+            const unsigned int f0 = reinterpret_cast<u32x4&>(a_frag[0])[d];
+            const unsigned int f1 = reinterpret_cast<u32x4&>(a_frag[1])[d];
+            const unsigned int f2 = reinterpret_cast<u32x4&>(a_frag[2])[d];
+            const unsigned int f3 = reinterpret_cast<u32x4&>(a_frag[3])[d];
+            const unsigned int lo = (cs_q & 1) ? f1 : f0;
+            const unsigned int hi = (cs_q & 1) ? f3 : f2;
+            sel[d] = (cs_q & 2) ? hi : lo;
+          }
+          const V8 av = reinterpret_cast<V8&>(sel);
+          if constexpr (std::is_same<V8, bf16x8>::value)
+            cs_acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, ones, cs_acc,
+                                                             0, 0, 0);
+          else
+            cs_acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, ones, cs_acc,
+                                                            0, 0, 0);
+        }
+      }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -436,16 +485,24 @@ void gemm_tn_sk_kernel(const T* __restrict__ A, const T* __restrict__ B,
       }
     }
   }
+  if constexpr (COLSUM) {
+    if (do_cs && ccol == 0) {
+      float* PS = P + (long)sm * N * K + (long)split * N;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const long n = n0 + wr + cs_q * 16 + crow_off + r;
+        if (n < N) PS[n] = cs_acc[r];
+      }
+    }
+  }
 }
 
 // fold the SM split partials and cast: C[n,k] = T(sum_s P[s,n,k])
 template <typename T>
-__global__ __launch_bounds__(256)
-void reduce_partials_kernel(const float* __restrict__ P, T* __restrict__ C,
-                            long NK, int sm) {
+__device__ __forceinline__ void fold_partials4(const float* __restrict__ P,
+                                               T* __restrict__ C, long i4,
+                                               long NK, int sm) {
   typedef float f4 __attribute__((ext_vector_type(4)));
-  const long i4 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i4 >= NK) return;
   f4 acc = *reinterpret_cast<const f4*>(P + i4);
   for (int s = 1; s < sm; ++s) {
     f4 v = *reinterpret_cast<const f4*>(P + (long)s * NK + i4);
@@ -454,6 +511,83 @@ void reduce_partials_kernel(const float* __restrict__ P, T* __restrict__ C,
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q) C[i4 + q] = from_f32<T>(acc[q]);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256)
+void reduce_partials_kernel(const float* __restrict__ P, T* __restrict__ C,
+                            long NK, int sm) {
+  const long i4 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i4 >= NK) return;
+  fold_partials4<T>(P, C, i4, NK, sm);
+}
+
+// same fold, plus (in the blocks past the dW ones) the column-sum slices
+// P[sm*NK + s*N + n] of the COLSUM kernel into CS[n] — one launch for both
+template <typename T>
+__global__ __launch_bounds__(256)
+void reduce_partials_colsum_kernel(const float* __restrict__ P,
+                                   T* __restrict__ C, T* __restrict__ CS,
+                                   long NK, long N, int sm, int rblocks) {
+  if ((int)blockIdx.x < rblocks) {
+    const long i4 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i4 >= NK) return;
+    fold_partials4<T>(P, C, i4, NK, sm);
+  } else {
+    const long i4 = ((long)(blockIdx.x - rblocks) * 256 + threadIdx.x) * 4;
+    if (i4 >= N) return;
+    fold_partials4<T>(P + (long)sm * NK, CS, i4, N, sm);
+  }
+}
+
+// split-M depth of the v2 path for an [M] contraction and tiles2 128x128
+// output tiles (shared by gemm_tn and gemm_tn_colsum so C stays identical)
+int tn_v2_split(long M, int tiles2) {
+  int sm = 1;
+  if (const char* env = getenv("PDNLP_TN_SM")) sm = atoi(env);
+  else if (tiles2 < 512)
+    // swept (gpurun_out/sweep_dgemm.log): sm4 wins for small outputs
+    // (<=108 tiles), sm2 everywhere else under 512 tiles — deeper splits
+    // pay more in fp32-partial traffic than they buy in grid fill
+    sm = tiles2 <= 108 ? 4 : 2;
+  if (sm < 1) sm = 1;
+  while (sm > 1 && M % (64L * sm) != 0) sm /= 2;
+  return sm;
+}
+
+bool tn_v2_ok(const torch::Tensor& A, long N, long K) {
+  return getenv("PDNLP_TN_V1") == nullptr
+      && getenv("PDNLP_TN_SERIAL") == nullptr
+      && N % 128 == 0 && K % 128 == 0
+      && (A.scalar_type() == torch::kBFloat16
+          || A.scalar_type() == torch::kHalf);
+}
+
+template <typename T, typename V8>
+void launch_tn_colsum(const torch::Tensor& A, const torch::Tensor& B,
+                      torch::Tensor& P, torch::Tensor& C, torch::Tensor& CS,
+                      long M, long N, long K, int tiles2, int sm,
+                      hipStream_t stream) {
+  const int nwg2 = tiles2 * sm;
+  const long NK = N * K;
+  const int rblocks = (int)((NK / 4 + 255) / 256);
+  const int cblocks = (int)((N / 4 + 255) / 256);
+  if (getenv("PDNLP_TN_SYNC") == nullptr)
+    hipLaunchKernelGGL((gemm_tn_sk_kernel<T, V8, true, false, true>),
+                       dim3(nwg2), dim3(512), 0, stream,
+                       (const T*)A.data_ptr(), (const T*)B.data_ptr(),
+                       (float*)P.data_ptr(), M, N, K, (int)(K / 128), tiles2,
+                       sm, nwg2);
+  else
+    hipLaunchKernelGGL((gemm_tn_sk_kernel<T, V8, false, false, true>),
+                       dim3(nwg2), dim3(512), 0, stream,
+                       (const T*)A.data_ptr(), (const T*)B.data_ptr(),
+                       (float*)P.data_ptr(), M, N, K, (int)(K / 128), tiles2,
+                       sm, nwg2);
+  hipLaunchKernelGGL((reduce_partials_colsum_kernel<T>),
+                     dim3(rblocks + cblocks), dim3(256), 0, stream,
+                     (const float*)P.data_ptr(), (T*)C.data_ptr(),
+                     (T*)CS.data_ptr(), NK, N, sm, rblocks);
 }
 
 }  // namespace
@@ -480,14 +614,7 @@ torch::Tensor gemm_tn(torch::Tensor A, torch::Tensor B) {
           || A.scalar_type() == torch::kHalf);
   if (v2_ok) {
     const int tiles2 = (int)((N / 128) * (K / 128));
-    int sm = 1;
-    if (const char* env = getenv("PDNLP_TN_SM")) sm = atoi(env);
-    else if (tiles2 < 512)
-      // swept (gpurun_out/sweep_dgemm.log): sm4 wins for small outputs
-      // (<=108 tiles), sm2 everywhere else under 512 tiles — deeper splits
-      // pay more in fp32-partial traffic than they buy in grid fill
-      sm = tiles2 <= 108 ? 4 : 2;
-    while (sm > 1 && M % (64L * sm) != 0) sm /= 2;
+    const int sm = tn_v2_split(M, tiles2);
     const int nwg2 = tiles2 * sm;
     auto P = torch::empty({sm, N, K},
                           A.options().dtype(torch::kFloat32));
@@ -577,4 +704,37 @@ torch::Tensor gemm_tn(torch::Tensor A, torch::Tensor B) {
     TORCH_CHECK(false, "gemm_tn: bf16/fp16 only");
   }
   return C;
+}
+
+torch::Tensor col_sum(torch::Tensor x);
+
+// {C, colsum} with C = gemm_tn(A, B) (bit-identical) and colsum[n] =
+// sum_m A[m, n] in A's dtype — the dW/db pair of a biased projection from
+// one pass over dY. On the v2 grid the sums ride along in the GEMM (see
+// COLSUM above); every other path computes C as gemm_tn does and takes the
+// sums from col_sum.
+std::vector<torch::Tensor> gemm_tn_colsum(torch::Tensor A, torch::Tensor B) {
+  TORCH_CHECK(A.is_cuda() && A.is_contiguous() && B.is_contiguous());
+  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.size(0) == B.size(0));
+  const long M = A.size(0), N = A.size(1), K = B.size(1);
+  if (!tn_v2_ok(A, N, K) || getenv("PDNLP_TN_PROBE") != nullptr)
+    return {gemm_tn(A, B), col_sum(A)};
+  TORCH_CHECK(M % BC == 0, "gemm_tn: M must be a multiple of 64");
+  TORCH_CHECK(A.scalar_type() == B.scalar_type(),
+              "gemm_tn_colsum: A and B dtypes differ");
+  auto C = torch::empty({N, K}, A.options());
+  auto CS = torch::empty({N}, A.options());
+  const int tiles2 = (int)((N / 128) * (K / 128));
+  const int sm = tn_v2_split(M, tiles2);
+  // dW partials [sm][N][K], then the column-sum slices [sm][N]
+  auto P = torch::empty({(long)sm * (N * K + N)},
+                        A.options().dtype(torch::kFloat32));
+  auto stream = at::hip::getCurrentHIPStream();
+  if (A.scalar_type() == torch::kBFloat16)
+    launch_tn_colsum<__hip_bfloat16, bf16x8>(A, B, P, C, CS, M, N, K, tiles2,
+                                             sm, stream);
+  else
+    launch_tn_colsum<__half, f16x8>(A, B, P, C, CS, M, N, K, tiles2, sm,
+                                    stream);
+  return {C, CS};
 }

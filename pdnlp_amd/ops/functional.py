@@ -164,6 +164,20 @@ def _tn_shape_ok(dy2, x2) -> bool:
             and x2.shape[1] % 64 == 0)
 
 
+def _tn_colsum_ok(dy2, x2, mode) -> bool:
+    """True when dW and the bias gradient come from ONE gemm_tn_colsum call
+    (the column sum of dY rides along in the first-party dW GEMM)."""
+    return (mode in ("hip", "auto") and _tn_shape_ok(dy2, x2)
+            and getattr(ext(), "gemm_tn_colsum", None) is not None)
+
+
+def _bias_grad(dy2):
+    if dy2.shape[-1] % 4 == 0 and dy2.shape[0] >= 256 \
+            and dy2.dtype != torch.float32:
+        return ext().col_sum(dy2)
+    return dy2.sum(0)
+
+
 class _LinearHipFn(torch.autograd.Function):
     """y = x @ w^T + b with the forward GEMM on the hand-written MFMA kernel
     (optionally fused activation); backward dGEMMs on first-party MFMA
@@ -206,17 +220,57 @@ class _LinearHipFn(torch.autograd.Function):
             dy2.record_stream(s)
             x2.record_stream(s)
             dw.record_stream(torch.cuda.current_stream())
+        elif ctx.has_bias and _tn_colsum_ok(dy2, x2, mode):
+            dw, db = ext().gemm_tn_colsum(dy2, x2)  # dW + db in one pass
         elif hip_dw and _tn_shape_ok(dy2, x2):
             dw = ext().gemm_tn(dy2, x2)   # first-party MFMA TN
         else:
             dw = dy2.t() @ x2             # rocBLAS TN
         if ctx.has_bias and db is None:
-            if dy2.shape[-1] % 4 == 0 and dy2.shape[0] >= 256 \
-                    and dy2.dtype != torch.float32:
-                db = ext().col_sum(dy2)
-            else:
-                db = dy2.sum(0)
+            db = _bias_grad(dy2)
         return dx.view(ctx.in_shape), dw, db, None
+
+
+class _LinearDeferredBiasHipFn(torch.autograd.Function):
+    """y = x @ w^T whose bias ``b`` is applied DOWNSTREAM (in the fused
+    bias+dropout+residual+LN epilogue). ``b`` is an input for gradient
+    purposes only: forward does not add it, backward returns its gradient
+    — the column sum of dy, which is also d(loss)/d(b) because the epilogue
+    adds ``b`` straight onto this output — from the dW GEMM that reads dy
+    anyway (``gemm_tn_colsum``) instead of a separate pass in the epilogue's
+    backward."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        x2 = x.contiguous().view(-1, x.shape[-1])
+        y, _ = ext().gemm_nt_fwd(x2, w, torch.Tensor(), "none")
+        ctx.save_for_backward(x2, w)
+        ctx.in_shape = x.shape
+        return y.view(*x.shape[:-1], w.shape[0])
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, w = ctx.saved_tensors
+        dy2 = dy.contiguous().view(-1, dy.shape[-1])
+        mode = _dgemm_mode()
+        hip_dx = (mode == "hip"
+                  or (mode == "auto"
+                      and not _nn_blas_faster(dy2.shape[0], w.shape[1])))
+        if hip_dx and _nn_shape_ok(dy2, w):
+            dx = ext().gemm_nn(dy2, w)
+        else:
+            dx = dy2 @ w
+        need_db = ctx.needs_input_grad[2]
+        db = None
+        if need_db and _tn_colsum_ok(dy2, x2, mode):
+            dw, db = ext().gemm_tn_colsum(dy2, x2)
+        elif mode in ("hip", "auto") and _tn_shape_ok(dy2, x2):
+            dw = ext().gemm_tn(dy2, x2)
+        else:
+            dw = dy2.t() @ x2
+        if need_db and db is None:
+            db = _bias_grad(dy2)
+        return dx.view(ctx.in_shape), dw, db
 
 
 class _LinearForkHipFn(torch.autograd.Function):
@@ -268,17 +322,15 @@ class _LinearForkHipFn(torch.autograd.Function):
                 dx = dy2 @ w
             if dpass is not None:
                 dx = dx + dpass.reshape(-1, dpass.shape[-1])
-        if mode in ("hip", "auto") and _tn_shape_ok(dy2, x2):
+        db = None
+        if ctx.has_bias and _tn_colsum_ok(dy2, x2, mode):
+            dw, db = ext().gemm_tn_colsum(dy2, x2)  # dW + db in one pass
+        elif mode in ("hip", "auto") and _tn_shape_ok(dy2, x2):
             dw = ext().gemm_tn(dy2, x2)
         else:
             dw = dy2.t() @ x2
-        db = None
-        if ctx.has_bias:
-            if dy2.shape[-1] % 4 == 0 and dy2.shape[0] >= 256 \
-                    and dy2.dtype != torch.float32:
-                db = ext().col_sum(dy2)
-            else:
-                db = dy2.sum(0)
+        if ctx.has_bias and db is None:
+            db = _bias_grad(dy2)
         return dx.view(ctx.in_shape), dw, db, None
 
 
@@ -561,6 +613,65 @@ def bias_dropout_residual_layernorm(
         h = F.dropout(h, p=p, training=True)
     h = h + residual
     return F.layer_norm(h, (h.shape[-1],), ln_w, ln_b, eps)
+
+
+class _BiasDropResLNNoDbFn(torch.autograd.Function):
+    """_BiasDropResLNFn whose bias has no gradient path here: the backward
+    skips the bias column sum (one of the three input streams of its
+    second pass). The producing projection returns that gradient
+    (_LinearDeferredBiasHipFn)."""
+
+    @staticmethod
+    def forward(ctx, y, bias, residual, ln_w, ln_b, p, training, eps):
+        p_eff = float(p if training else 0.0)
+        if p_eff > 0.0:
+            seed_buf, salt = _dropout_seed.get(y.device)
+        else:
+            seed_buf, salt = torch.Tensor(), 0
+        out, xsum, mask, mean, rstd = ext().bias_dropout_residual_ln_fwd(
+            y.contiguous(), bias, residual.contiguous(), ln_w, ln_b,
+            p_eff, eps, seed_buf, salt)
+        ctx.save_for_backward(xsum, mask, ln_w, mean, rstd)
+        ctx.p = p_eff
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        xsum, mask, ln_w, mean, rstd = ctx.saved_tensors
+        dy, dres, dlnw, dlnb = ext().bias_dropout_residual_ln_bwd_nodb(
+            dout.contiguous(), xsum, mask, ln_w, mean, rstd, ctx.p)
+        return dy, None, dres, dlnw, dlnb, None, None, None
+
+
+def linear_bias_dropout_residual_layernorm(
+        x: torch.Tensor, w: torch.Tensor, b: torch.Tensor,
+        residual: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor,
+        p: float = 0.1, training: bool = False,
+        eps: float = 1e-12) -> torch.Tensor:
+    """out = LN(dropout(x @ w^T + b) + residual): a projection whose bias is
+    applied in the fused epilogue (attention-output and FFN-down).
+
+    On HIP, with the first-party dW GEMM in use, the bias gradient is taken
+    inside that GEMM (``gemm_tn_colsum``) and the epilogue's backward no
+    longer sums dy for it. Everywhere else this is exactly
+    ``bias_dropout_residual_layernorm(linear(x, w, None), b, ...)``."""
+    import os
+    H = w.shape[0]
+    rows = x.numel() // x.shape[-1]
+    if hip_enabled(x) and H % 256 == 0 and H <= 1024 \
+            and os.environ.get("PDNLP_FWD") != "blas" \
+            and _dgemm_mode() in ("hip", "auto") \
+            and not dw_stream.enabled() \
+            and getattr(ext(), "gemm_nt_fwd", None) is not None \
+            and getattr(ext(), "gemm_tn_colsum", None) is not None \
+            and getattr(ext(), "bias_dropout_residual_ln_bwd_nodb",
+                        None) is not None \
+            and _gemm_shape_ok(x, w) and rows % 64 == 0:
+        proj = _LinearDeferredBiasHipFn.apply(x, w, b)
+        return _BiasDropResLNNoDbFn.apply(
+            proj, b.detach(), residual, ln_w, ln_b, p, training, eps)
+    return bias_dropout_residual_layernorm(
+        linear(x, w, None), b, residual, ln_w, ln_b, p, training, eps)
 
 
 # --------------------------------------------------------------------------
