@@ -61,8 +61,7 @@ class GradScaler:
             return
         inv = 1.0 / self._scale
         grads = list(self._grads(optimizer))
-        if grads and hip_enabled(grads[0]) and \
-                getattr(ext(), "multi_tensor_unscale", None) is not None:
+        if grads and hip_enabled(grads[0]):
             dev = grads[0].device
             if self._found_dev is None or self._found_dev.device != dev:
                 self._found_dev = torch.zeros(1, dtype=torch.float32,

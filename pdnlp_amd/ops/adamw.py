@@ -35,7 +35,7 @@ def multi_tensor_adamw(params: List[torch.Tensor], grads: List[torch.Tensor],
         return
     bc1 = 1.0 - beta1 ** step
     bc2 = 1.0 - beta2 ** step
-    if hip_enabled(params[0]) and getattr(ext(), "multi_tensor_adamw", None) is not None:
+    if hip_enabled(params[0]):
         use_master = masters[0] is not None
         finf = found_inf if found_inf is not None else torch.Tensor()
         for i in range(0, len(params), CHUNK):
@@ -147,8 +147,7 @@ class FusedSGD(torch.optim.Optimizer):
                 if p.grad is None:
                     continue
                 state = self.state[p]
-                if hip_enabled(p) and getattr(ext(), "multi_tensor_sgd",
-                                              None) is not None:
+                if hip_enabled(p):
                     hip = True
                     if "momentum_buffer" not in state:
                         state["momentum_buffer"] = torch.zeros_like(

@@ -29,23 +29,11 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "common.h"
+#include "gemm_common.h"  // vector typedefs, mfma16
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int NTHREADS = 256;  // 4 waves
-
-template <typename V8>
-__device__ __forceinline__ f32x4 mfma16(V8 a, V8 b, f32x4 c) {
-  if constexpr (std::is_same<V8, bf16x8>::value)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
 
 template <typename T>
 __device__ __forceinline__ unsigned short f32_bits16(float v) {
@@ -118,7 +106,6 @@ __device__ __forceinline__ unsigned int tr_base(const char* lds, int ent0,
 // four transposed fragments in ONE asm block (8x ds_read_b64_tr_b16 +
 // s_waitcnt INSIDE — the compiler cannot count asm ds ops, and the outputs
 // must be earlyclobber so they never alias the address inputs).
-typedef unsigned int uint2v __attribute__((ext_vector_type(2)));
 template <typename V8>
 __device__ __forceinline__ void read_tr4(unsigned int b0, unsigned int b1,
                                          unsigned int b2, unsigned int b3,

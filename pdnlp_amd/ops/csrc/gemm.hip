@@ -34,58 +34,15 @@
 
 #include <cstdlib>
 
-#include "common.h"
+#include "gemm_common.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BK = 64;
 constexpr int NTHREADS = 256;
 
 __device__ __forceinline__ float gelu_f2(float x) {
   return 0.5f * x * (1.f + erff(x * 0.70710678118654752f));
-}
-
-// stage a ROWS x BK tile (row stride `ld` elements) into LDS via
-// global_load_lds. Linear LDS image [ROWS][128 bytes]; the XOR swizzle is
-// pre-applied on the source byte offset. Each wave-instruction moves 8 rows
-// (8 lanes of 16 B per row); 4 waves x (ROWS/32) calls cover ROWS rows.
-template <typename T, int ROWS, int NW>
-__device__ __forceinline__ void stage_tile(const T* __restrict__ src, long ld,
-                                           long row0, long max_row, long k0,
-                                           char* lds) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x >> 6;
-  const int sub_row = lane >> 3;           // 0..7
-  const int piece = lane & 7;              // 16B piece within the 128B row
-  const int kbyte = (piece * 16) ^ (sub_row << 4);  // source pre-swizzle
-  constexpr int CPW = ROWS / (8 * NW);     // 8-row chunks per wave
-#pragma unroll
-  for (int c = 0; c < CPW; ++c) {
-    const int r = (wid * CPW + c) * 8 + sub_row;
-    long gr = row0 + r;
-    gr = gr < max_row ? gr : max_row - 1;        // clamp tail (stores guard)
-    const char* gp = (const char*)(src + gr * ld + k0) + kbyte;
-    // LDS dest operand is WAVE-UNIFORM (start of this call's 8-row chunk);
-    // hardware writes lane l at dest + l*16 = row (l>>3), piece (l&7).
-    char* lp = lds + (long)(wid * CPW + c) * 8 * 128;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) unsigned int*)gp,
-        (__attribute__((address_space(3))) unsigned int*)lp, 16, 0, 0);
-  }
-}
-
-// read one 16x(8k) fragment from the swizzled LDS image
-template <typename V8>
-__device__ __forceinline__ V8 read_frag(const char* lds, int frag_row0,
-                                        int ks) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int row = frag_row0 + (lane & 15);
-  const int colbyte = (ks * 64 + (lane >> 4) * 16) ^ ((row & 7) << 4);
-  return *reinterpret_cast<const V8*>(lds + row * 128 + colbyte);
 }
 
 enum Act { ACT_NONE = 0, ACT_GELU = 1, ACT_TANH = 2 };
@@ -107,13 +64,7 @@ void gemm_nt_kernel(const T* __restrict__ A, const T* __restrict__ W,
   constexpr int RM = TM / 16, RN = TN / 16;     // fragment repeats
 
   // XCD-aware bijective remap of the tile id (guide T1)
-  int wg = blockIdx.x;
-  {
-    const int nxcd = 8;
-    const int q = nwg / nxcd, r = nwg % nxcd;
-    const int xcd = wg % nxcd, idx = wg / nxcd;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const long tile_m = wg / tiles_n, tile_n = wg % tiles_n;
   const long m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -163,13 +114,7 @@ void gemm_nt_kernel(const T* __restrict__ A, const T* __restrict__ W,
       for (int i = 0; i < RM; ++i) {
 #pragma unroll
         for (int j = 0; j < RN; ++j) {
-          if constexpr (std::is_same<V8, bf16x8>::value) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-          } else {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-          }
+          acc[i][j] = mfma16<V8>(a_frag[i], b_frag[j], acc[i][j]);
         }
       }
     }
@@ -225,13 +170,7 @@ void gemm_nt_pipe_kernel(const T* __restrict__ A, const T* __restrict__ W,
   constexpr int RM = TM / 16, RN = TN / 16;
   constexpr int NGLDS = BM / (8 * NW) + BN / (8 * NW);  // glds per wave/tile
 
-  int wg = blockIdx.x;
-  {
-    const int nxcd = 8;
-    const int q = nwg / nxcd, r = nwg % nxcd;
-    const int xcd = wg % nxcd, idx = wg / nxcd;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const long tile_m = wg / tiles_n, tile_n = wg % tiles_n;
   const long m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -280,13 +219,7 @@ void gemm_nt_pipe_kernel(const T* __restrict__ A, const T* __restrict__ W,
       for (int i = 0; i < RM; ++i) {
 #pragma unroll
         for (int j = 0; j < RN; ++j) {
-          if constexpr (std::is_same<V8, bf16x8>::value) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-          } else {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-          }
+          acc[i][j] = mfma16<V8>(a_frag[i], b_frag[j], acc[i][j]);
         }
       }
     }
@@ -339,13 +272,7 @@ void gemm_nt_rs_kernel(const T* __restrict__ A, const T* __restrict__ W,
   constexpr int TM = BM / WM, TN = BN / WN;   // 64 x 32
   constexpr int RM = TM / 16, RN = TN / 16;   // 4 x 2
 
-  int wg = blockIdx.x;
-  {
-    const int nxcd = 8;
-    const int q = nwg / nxcd, r = nwg % nxcd;
-    const int xcd = wg % nxcd, idx = wg / nxcd;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const long tile_m = wg / tiles_n, tile_n = wg % tiles_n;
   const long m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -414,13 +341,7 @@ void gemm_nt_rs_kernel(const T* __restrict__ A, const T* __restrict__ W,
       for (int i = 0; i < RM; ++i) {
 #pragma unroll
         for (int j = 0; j < RN; ++j) {
-          if constexpr (std::is_same<V8, bf16x8>::value) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-          } else {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-          }
+          acc[i][j] = mfma16<V8>(a_frag[i], b_frag[j], acc[i][j]);
         }
       }
     }
@@ -471,13 +392,7 @@ void gemm_nt_3b_kernel(const T* __restrict__ A, const T* __restrict__ W,
   constexpr int TM = BM / WM, TN = BN / WN;   // 32 x 16
   constexpr int RM = TM / 16, RN = TN / 16;   // 2 x 1
 
-  int wg = blockIdx.x;
-  {
-    const int nxcd = 8;
-    const int q = nwg / nxcd, r = nwg % nxcd;
-    const int xcd = wg % nxcd, idx = wg / nxcd;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const long tile_m = wg / tiles_n, tile_n = wg % tiles_n;
   const long m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -526,13 +441,7 @@ void gemm_nt_3b_kernel(const T* __restrict__ A, const T* __restrict__ W,
       for (int i = 0; i < RM; ++i) {
 #pragma unroll
         for (int j = 0; j < RN; ++j) {
-          if constexpr (std::is_same<V8, bf16x8>::value) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-          } else {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-          }
+          acc[i][j] = mfma16<V8>(a_frag[i], b_frag[j], acc[i][j]);
         }
       }
     }

@@ -11,8 +11,8 @@
 //  - A (dY) staged exactly like gemm.hip's A: [BM rows][64 contraction]
 //    XOR-swizzled 128-byte-row LDS image via global_load_lds, fragments as
 //    plain 16-B ds_reads.
-//  - B (W) staged per 64-column group into the gfx950 tr-read image of
-//    gemm_tn.hip and consumed with ds_read_b64_tr_b16 hardware
+//  - B (W) staged per 64-column group into the gfx950 tr-read image
+//    (gemm_common.h) and consumed with ds_read_b64_tr_b16 hardware
 //    transpose-reads (guide T10) — no per-lane b16 gathers.
 //  - BK=64 contraction chunks, double-buffered, one vmcnt(0)+barrier per
 //    chunk; 4- or 8-wave wave grids; fp32 accumulation; XCD-aware block
@@ -24,129 +24,16 @@
 
 #include <cstdlib>
 
-#include "common.h"
+#include "gemm_common.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int uint2v __attribute__((ext_vector_type(2)));
-
 constexpr int BK = 64;   // contraction chunk
 
-// ---- A-operand staging/reading (as gemm.hip) ------------------------------
-template <typename T, int ROWS, int NW>
-__device__ __forceinline__ void stage_tile(const T* __restrict__ src, long ld,
-                                           long row0, long max_row, long k0,
-                                           char* lds) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x >> 6;
-  const int sub_row = lane >> 3;
-  const int piece = lane & 7;
-  const int kbyte = (piece * 16) ^ (sub_row << 4);
-  constexpr int CPW = ROWS / (8 * NW);
-#pragma unroll
-  for (int c = 0; c < CPW; ++c) {
-    const int r = (wid * CPW + c) * 8 + sub_row;
-    long gr = row0 + r;
-    gr = gr < max_row ? gr : max_row - 1;
-    const char* gp = (const char*)(src + gr * ld + k0) + kbyte;
-    char* lp = lds + (long)(wid * CPW + c) * 8 * 128;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) unsigned int*)gp,
-        (__attribute__((address_space(3))) unsigned int*)lp, 16, 0, 0);
-  }
-}
-
-template <typename V8>
-__device__ __forceinline__ V8 read_frag(const char* lds, int frag_row0,
-                                        int ks) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int row = frag_row0 + (lane & 15);
-  const int colbyte = (ks * 64 + (lane >> 4) * 16) ^ ((row & 7) << 4);
-  return *reinterpret_cast<const V8*>(lds + row * 128 + colbyte);
-}
-
-// ---- B-operand tr image (as gemm_tn.hip, NW-templated staging) ------------
-// stage a [64 contraction-rows][64 cols] tile of `src` (row stride ld) into
-// the 8-KB tr-read image: 8 subtiles x 1024 B, each filled by one
-// global_load_lds wave-instruction with every lane fetching 16 contiguous
-// bytes of one global row (coalesced).
-template <typename T, int NW>
-__device__ __forceinline__ void stage_tr(const T* __restrict__ src, long ld,
-                                         long m0, long max_m, long col0,
-                                         char* lds) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x >> 6;
-  const int m_rel = ((lane >> 3) & 3) * 8 + (lane >> 5) * 4 + ((lane >> 1) & 3);
-  const int c0 = (lane & 1) * 8;
-  constexpr int SPW = 8 / NW;          // subtiles per wave
-#pragma unroll
-  for (int s = 0; s < SPW; ++s) {
-    const int sub = wid * SPW + s;
-    const int s_m = sub >> 2;
-    const int s_c = sub & 3;
-    long gm = m0 + s_m * 32 + m_rel;
-    gm = gm < max_m ? gm : max_m - 1;
-    const char* gp = (const char*)(src + gm * ld + col0 + s_c * 16 + c0);
-    char* lp = lds + sub * 1024;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) unsigned int*)gp,
-        (__attribute__((address_space(3))) unsigned int*)lp, 16, 0, 0);
-  }
-}
-
-__device__ __forceinline__ unsigned int frag_tr_base(const char* lds, int ent0,
-                                                     int m_sub) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int sub = (m_sub >> 5) * 4 + (ent0 >> 4);
-  return (unsigned int)(unsigned long)lds + sub * 1024 + (lane & 15) * 8 +
-         (lane >> 4) * 128;
-}
-
-// two transposed fragments in ONE asm block (4x ds_read_b64_tr_b16, one
-// lgkmcnt(0) INSIDE — the compiler cannot count asm ds ops; outputs
-// EARLYCLOBBER or LLVM aliases them with still-needed address inputs)
-template <typename V8>
-__device__ __forceinline__ void frag_tr2(unsigned int a0, unsigned int a1,
-                                         V8* f) {
-  uint2v r0, r1, r2, r3;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %4\n\t"
-      "ds_read_b64_tr_b16 %1, %4 offset:512\n\t"
-      "ds_read_b64_tr_b16 %2, %5\n\t"
-      "ds_read_b64_tr_b16 %3, %5 offset:512\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)
-      : "v"(a0), "v"(a1)
-      : "memory");
-  reinterpret_cast<uint2v*>(&f[0])[0] = r0;
-  reinterpret_cast<uint2v*>(&f[0])[1] = r1;
-  reinterpret_cast<uint2v*>(&f[1])[0] = r2;
-  reinterpret_cast<uint2v*>(&f[1])[1] = r3;
-}
-
-template <typename V8>
-__device__ __forceinline__ V8 frag_tr1(unsigned int a0) {
-  uint2v r0, r1;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %2\n\t"
-      "ds_read_b64_tr_b16 %1, %2 offset:512\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(r0), "=&v"(r1)
-      : "v"(a0)
-      : "memory");
-  V8 f;
-  reinterpret_cast<uint2v*>(&f)[0] = r0;
-  reinterpret_cast<uint2v*>(&f)[1] = r1;
-  return f;
-}
-
-// ---- the kernel -----------------------------------------------------------
+// A (dY) uses the row-major image (stage_tile/read_frag), B (W) the tr-read
+// image (stage_tr/frag_tr*) of gemm_common.h.
 template <typename T, typename V8, int BM, int BN, int NW,
-          bool RAWBAR = false, bool ADDD = false,
-          bool NOSYNC = false>  // TIMING PROBE ONLY: numerics invalid
+          bool RAWBAR = false, bool ADDD = false>
 __global__ __launch_bounds__(NW * WAVE)
 void gemm_nn_kernel(const T* __restrict__ A, const T* __restrict__ B,
                     T* __restrict__ C, long M, long N, long K,
@@ -159,13 +46,7 @@ void gemm_nn_kernel(const T* __restrict__ A, const T* __restrict__ B,
   // glds wave-instructions per buffer (for the counted-vmcnt schedule)
   constexpr int GLDS = BM / (8 * NW) + NGB * (8 / NW);
 
-  int wg = blockIdx.x;
-  {
-    const int nxcd = 8;
-    const int q = nwg / nxcd, r = nwg % nxcd;
-    const int xcd = wg % nxcd, idx = wg / nxcd;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const long tile_m = wg / tiles_n, tile_n = wg % tiles_n;
   const long m0 = tile_m * BM, k0 = tile_n * BN;
 
@@ -208,7 +89,7 @@ void gemm_nn_kernel(const T* __restrict__ A, const T* __restrict__ B,
                      : "memory");
       else
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      if constexpr (!NOSYNC) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
     }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
@@ -233,19 +114,13 @@ void gemm_nn_kernel(const T* __restrict__ A, const T* __restrict__ B,
       for (int i = 0; i < RM; ++i) {
 #pragma unroll
         for (int j = 0; j < RN; ++j) {
-          if constexpr (std::is_same<V8, bf16x8>::value) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-          } else {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-          }
+          acc[i][j] = mfma16<V8>(a_frag[i], b_frag[j], acc[i][j]);
         }
       }
     }
     if constexpr (RAWBAR) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if constexpr (!NOSYNC) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
@@ -291,13 +166,7 @@ void gemm_nn_256_kernel(const T* __restrict__ A, const T* __restrict__ B,
   constexpr int NGB = BN / 64;
   constexpr int GLDS = BM / (8 * NW) + NGB * (8 / NW);  // 4 + 2 = 6
 
-  int wg = blockIdx.x;
-  {
-    const int nxcd = 8;
-    const int q = nwg / nxcd, r = nwg % nxcd;
-    const int xcd = wg % nxcd, idx = wg / nxcd;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const long tile_m = wg / tiles_n, tile_n = wg % tiles_n;
   const long m0 = tile_m * BM, k0 = tile_n * BN;
 
@@ -350,13 +219,7 @@ void gemm_nn_256_kernel(const T* __restrict__ A, const T* __restrict__ B,
       for (int i = 0; i < RM; ++i) {
 #pragma unroll
         for (int j = 0; j < RN; ++j) {
-          if constexpr (std::is_same<V8, bf16x8>::value) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-          } else {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-          }
+          acc[i][j] = mfma16<V8>(a_frag[i], b_frag[j], acc[i][j]);
         }
       }
     }
@@ -426,14 +289,6 @@ void launch_nn(const torch::Tensor& A, const torch::Tensor& B,
   const int nwg = tiles_m * tiles_n;
   const bool w8 = std::getenv("PDNLP_NN_W4") == nullptr;  // 8 waves default
   const bool rb = std::getenv("PDNLP_NN_RB") != nullptr;
-  // TIMING PROBE (numerics INVALID): barrier-free bound, 64x64w8 only
-  if (std::getenv("PDNLP_NN_PROBE") != nullptr && dptr == nullptr) {
-    hipLaunchKernelGGL((gemm_nn_kernel<T, V8, 64, 64, 8, true, false, true>),
-                       dim3(nwg), dim3(512), 0, stream,
-                       (const T*)A.data_ptr(), (const T*)B.data_ptr(),
-                       (T*)C.data_ptr(), M, N, K, tiles_n, nwg);
-    return;
-  }
   if (dptr != nullptr) {
     // fused +D epilogue: instantiated for the default tiles only
 #define LAUNCH_NN_D(BMV, BNV, NWV)                                             \

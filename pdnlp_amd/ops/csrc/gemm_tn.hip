@@ -8,15 +8,10 @@
 //  - 64x64 output tile, contraction chunked by 64, 4 waves (2x2) each
 //    owning a 32x32 sub-tile -> 432-576 workgroups on the BERT shapes
 //    (fills the 256 CUs without split-K).
-//  - Both operands are consumed TRANSPOSED (rows of dY^T / X^T). Instead of
-//    per-lane b16 gathers this uses gfx950's ds_read_b64_tr_b16 hardware
-//    transpose-read (guide T10): each 4-lane cluster reads 4 rows of a 4x4
-//    bf16 block (8-B aligned) and receives the block column-major.
-//  - The LDS image for a [32 m][16 col] subtile is the tr-read layout
-//    addr(m, c) = c + (m&3)*16 + (m>>3)*64 + ((m>>2)&1)*256 (elements),
-//    built directly by global_load_lds: dest element run l*8..l*8+7 decodes
-//    to (m_rel = ((l>>3)&3)*8 + (l>>5)*4 + ((l>>1)&3), c0 = (l&1)*8), i.e.
-//    each lane fetches 16 contiguous bytes of one global row — coalesced.
+//  - Both operands are consumed TRANSPOSED (rows of dY^T / X^T): both are
+//    staged into the tr-read LDS image and read with gfx950's
+//    ds_read_b64_tr_b16 hardware transpose-read (layout and lane math in
+//    gemm_common.h) instead of per-lane b16 gathers.
 //  - fp32 accumulation, bf16/fp16 C write, double-buffered staging.
 
 #include <torch/extension.h>
@@ -24,141 +19,22 @@
 
 #include <cstdlib>
 
-#include "common.h"
+#include "gemm_common.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int uint2v __attribute__((ext_vector_type(2)));
 
 constexpr int NTHREADS = 256;
 constexpr int BT = 64;   // output tile is BT x BT
 constexpr int BC = 64;   // contraction chunk
 
-// stage a [BC m][BT cols] tile of `src` (row stride ld) into the tr-read
-// image. 8 subtiles of 512 elements; one glds wave-instruction fills one
-// subtile; NW waves x (8/NW) calls cover the tile. Rows clamped to max_m.
-template <typename T, int NW>
-__device__ __forceinline__ void stage_tr(const T* __restrict__ src, long ld,
-                                         long m0, long max_m, long col0,
-                                         char* lds) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x >> 6;
-  // lane -> (m_rel within 32, c half) inside one subtile
-  const int m_rel = ((lane >> 3) & 3) * 8 + (lane >> 5) * 4 + ((lane >> 1) & 3);
-  const int c0 = (lane & 1) * 8;
-  constexpr int SPW = 8 / NW;
-#pragma unroll
-  for (int s = 0; s < SPW; ++s) {
-    const int sub = wid * SPW + s;        // subtile 0..7
-    const int s_m = sub >> 2;             // m half (0: m 0..31, 1: 32..63)
-    const int s_c = sub & 3;              // 16-col group
-    long gm = m0 + s_m * 32 + m_rel;
-    gm = gm < max_m ? gm : max_m - 1;
-    const char* gp = (const char*)(src + gm * ld + col0 + s_c * 16 + c0);
-    char* lp = lds + sub * 1024;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) unsigned int*)gp,
-        (__attribute__((address_space(3))) unsigned int*)lp, 16, 0, 0);
-  }
-}
-
-// per-lane base address of the transposed fragment at (ent0, m_sub):
-// lane l will receive data[ent0 + (l&15)][m_sub + (l>>4)*8 + i], i = 0..7.
-__device__ __forceinline__ unsigned int frag_tr_base(const char* lds, int ent0,
-                                                     int m_sub) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int sub = (m_sub >> 5) * 4 + (ent0 >> 4);
-  // lane-LINEAR 8-B addresses over each quarter's 128-B [4m][16c] block —
-  // the hardware transposes within the block (guide T10: "no internal lane
-  // offset"); wrong per-lane math here silently feeds scrambled operands.
-  return (unsigned int)(unsigned long)lds + sub * 1024 + (lane & 15) * 8 +
-         (lane >> 4) * 128;
-}
-
-// 4 transposed fragments (2 A + 2 B) in ONE asm block: 8x
-// ds_read_b64_tr_b16 then s_waitcnt lgkmcnt(0) INSIDE the block — the
-// compiler cannot count asm ds ops, so the wait must come before the
-// outputs escape the block.
-template <typename V8>
-__device__ __forceinline__ void frag_tr4(unsigned int a0, unsigned int a1,
-                                         unsigned int b0, unsigned int b1,
-                                         V8* af, V8* bf) {
-  uint2v r0, r1, r2, r3, r4, r5, r6, r7;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %8\n\t"
-      "ds_read_b64_tr_b16 %1, %8 offset:512\n\t"
-      "ds_read_b64_tr_b16 %2, %9\n\t"
-      "ds_read_b64_tr_b16 %3, %9 offset:512\n\t"
-      "ds_read_b64_tr_b16 %4, %10\n\t"
-      "ds_read_b64_tr_b16 %5, %10 offset:512\n\t"
-      "ds_read_b64_tr_b16 %6, %11\n\t"
-      "ds_read_b64_tr_b16 %7, %11 offset:512\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5),
-        "=&v"(r6), "=&v"(r7)
-      : "v"(a0), "v"(a1), "v"(b0), "v"(b1)
-      : "memory");
-  reinterpret_cast<uint2v*>(&af[0])[0] = r0;
-  reinterpret_cast<uint2v*>(&af[0])[1] = r1;
-  reinterpret_cast<uint2v*>(&af[1])[0] = r2;
-  reinterpret_cast<uint2v*>(&af[1])[1] = r3;
-  reinterpret_cast<uint2v*>(&bf[0])[0] = r4;
-  reinterpret_cast<uint2v*>(&bf[0])[1] = r5;
-  reinterpret_cast<uint2v*>(&bf[1])[0] = r6;
-  reinterpret_cast<uint2v*>(&bf[1])[1] = r7;
-}
-
-template <typename V8>
-__device__ __forceinline__ void frag_tr2(unsigned int a0, unsigned int a1,
-                                         V8* f) {
-  uint2v r0, r1, r2, r3;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %4\n\t"
-      "ds_read_b64_tr_b16 %1, %4 offset:512\n\t"
-      "ds_read_b64_tr_b16 %2, %5\n\t"
-      "ds_read_b64_tr_b16 %3, %5 offset:512\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)
-      : "v"(a0), "v"(a1)
-      : "memory");
-  reinterpret_cast<uint2v*>(&f[0])[0] = r0;
-  reinterpret_cast<uint2v*>(&f[0])[1] = r1;
-  reinterpret_cast<uint2v*>(&f[1])[0] = r2;
-  reinterpret_cast<uint2v*>(&f[1])[1] = r3;
-}
-
-template <typename V8>
-__device__ __forceinline__ V8 frag_tr1(unsigned int a0) {
-  uint2v r0, r1;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %2\n\t"
-      "ds_read_b64_tr_b16 %1, %2 offset:512\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(r0), "=&v"(r1)
-      : "v"(a0)
-      : "memory");
-  V8 f;
-  reinterpret_cast<uint2v*>(&f)[0] = r0;
-  reinterpret_cast<uint2v*>(&f)[1] = r1;
-  return f;
-}
-
-template <typename T, typename V8, bool PREFETCH>
+// 4-wave 64x64 kernel (PDNLP_TN_W4): 2x2 waves, a 32x32 sub-tile each
+template <typename T, typename V8>
 __global__ __launch_bounds__(NTHREADS)
 void gemm_tn_kernel(const T* __restrict__ A, const T* __restrict__ B,
                     T* __restrict__ C, long M, long N, long K,
                     int tiles_k, int nwg) {
   // XCD-aware bijective remap (guide T1)
-  int wg = blockIdx.x;
-  {
-    const int nxcd = 8;
-    const int q = nwg / nxcd, r = nwg % nxcd;
-    const int xcd = wg % nxcd, idx = wg / nxcd;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const long n0 = (wg / tiles_k) * BT, k0 = (wg % tiles_k) * BT;
 
   __shared__ __attribute__((aligned(16))) char lds_a[2][BC * BT * 2];
@@ -178,15 +54,9 @@ void gemm_tn_kernel(const T* __restrict__ A, const T* __restrict__ B,
   const int nchunks = (int)(M / BC);
   int cur = 0;
   for (int t = 0; t < nchunks; ++t) {
-    if (PREFETCH && t + 1 < nchunks) {
+    if (t + 1 < nchunks) {
       stage_tr<T, 4>(A, N, (long)(t + 1) * BC, M, n0, lds_a[cur ^ 1]);
       stage_tr<T, 4>(B, K, (long)(t + 1) * BC, M, k0, lds_b[cur ^ 1]);
-    }
-    if (!PREFETCH && t > 0) {
-      stage_tr<T, 4>(A, N, (long)t * BC, M, n0, lds_a[0]);
-      stage_tr<T, 4>(B, K, (long)t * BC, M, k0, lds_b[0]);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
     }
 #pragma unroll
     for (int ms = 0; ms < 2; ++ms) {
@@ -200,19 +70,13 @@ void gemm_tn_kernel(const T* __restrict__ A, const T* __restrict__ B,
       for (int i = 0; i < 2; ++i) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          if constexpr (std::is_same<V8, bf16x8>::value) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-          } else {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-          }
+          acc[i][j] = mfma16<V8>(a_frag[i], b_frag[j], acc[i][j]);
         }
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (PREFETCH) cur ^= 1;
+    cur ^= 1;
   }
 
   const int crow_off = (lane >> 4) * 4;
@@ -241,13 +105,7 @@ __global__ __launch_bounds__(512)
 void gemm_tn_w8_kernel(const T* __restrict__ A, const T* __restrict__ B,
                        T* __restrict__ C, long M, long N, long K,
                        int tiles_k, int nwg) {
-  int wg = blockIdx.x;
-  {
-    const int nxcd = 8;
-    const int q = nwg / nxcd, r = nwg % nxcd;
-    const int xcd = wg % nxcd, idx = wg / nxcd;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const long n0 = (wg / tiles_k) * BT, k0 = (wg % tiles_k) * BT;
 
   __shared__ __attribute__((aligned(16))) char lds_a[2][BC * BT * 2];
@@ -279,13 +137,7 @@ void gemm_tn_w8_kernel(const T* __restrict__ A, const T* __restrict__ B,
       V8 b_frag = frag_tr1<V8>(frag_tr_base(lds_b[cur], wc, ms * 32));
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        if constexpr (std::is_same<V8, bf16x8>::value) {
-          acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a_frag[i], b_frag, acc[i], 0, 0, 0);
-        } else {
-          acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-              a_frag[i], b_frag, acc[i], 0, 0, 0);
-        }
+        acc[i] = mfma16<V8>(a_frag[i], b_frag, acc[i]);
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -330,22 +182,14 @@ void gemm_tn_w8_kernel(const T* __restrict__ A, const T* __restrict__ B,
 // wave issues 9 MFMAs per ms step instead of 8. The fp32 slices land behind
 // the dW partials, P[sm*N*K + split*N + n], without atomics. The dW
 // accumulators are untouched, so C is bit-identical to the plain kernel's.
-template <typename T, typename V8, bool RAWBAR = false,
-          bool NOSYNC = false,  // TIMING PROBE ONLY: numerics invalid
-          bool COLSUM = false>
+template <typename T, typename V8, bool RAWBAR, bool COLSUM>
 __global__ __launch_bounds__(512)
 void gemm_tn_sk_kernel(const T* __restrict__ A, const T* __restrict__ B,
                        float* __restrict__ P, long M, long N, long K,
                        int tiles_k, int ntiles, int sm, int nwg) {
   constexpr int BTN = 128, BTK = 128;
   constexpr int GLDS = 4;  // stage_tr wave-instructions per buffer
-  int wg = blockIdx.x;
-  {
-    const int nxcd = 8;
-    const int q = nwg / nxcd, r = nwg % nxcd;
-    const int xcd = wg % nxcd, idx = wg / nxcd;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const int split = wg / ntiles;
   const int tile = wg % ntiles;
   const long n0 = (tile / tiles_k) * BTN, k0 = (tile % tiles_k) * BTK;
@@ -395,7 +239,7 @@ void gemm_tn_sk_kernel(const T* __restrict__ A, const T* __restrict__ B,
                      : "memory");
       else
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      if constexpr (!NOSYNC) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
     }
 #pragma unroll
     for (int ms = 0; ms < 2; ++ms) {
@@ -436,31 +280,20 @@ void gemm_tn_sk_kernel(const T* __restrict__ A, const T* __restrict__ B,
             sel[d] = (cs_q & 2) ? hi : lo;
           }
           const V8 av = reinterpret_cast<V8&>(sel);
-          if constexpr (std::is_same<V8, bf16x8>::value)
-            cs_acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, ones, cs_acc,
-                                                             0, 0, 0);
-          else
-            cs_acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, ones, cs_acc,
-                                                            0, 0, 0);
+          cs_acc = mfma16<V8>(av, ones, cs_acc);
         }
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          if constexpr (std::is_same<V8, bf16x8>::value) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-          } else {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                a_frag[i], b_frag[j], acc[i][j], 0, 0, 0);
-          }
+          acc[i][j] = mfma16<V8>(a_frag[i], b_frag[j], acc[i][j]);
         }
       }
     }
     if constexpr (RAWBAR) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if constexpr (!NOSYNC) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
@@ -555,46 +388,69 @@ int tn_v2_split(long M, int tiles2) {
   return sm;
 }
 
-bool tn_v2_ok(const torch::Tensor& A, long N, long K) {
-  return getenv("PDNLP_TN_V1") == nullptr
-      && getenv("PDNLP_TN_SERIAL") == nullptr
-      && N % 128 == 0 && K % 128 == 0
-      && (A.scalar_type() == torch::kBFloat16
-          || A.scalar_type() == torch::kHalf);
+// v2 (default): 128x128 tiles + split-M + fp32 partials when on-grid
+bool tn_v2_ok(long N, long K) {
+  return getenv("PDNLP_TN_V1") == nullptr && N % 128 == 0 && K % 128 == 0;
 }
 
+// v2 launches: gemm_tn_sk_kernel into the partials P, then the fold into C
+// (and CS when `colsum`). `sync` picks the vmcnt(0)+__syncthreads schedule
+// over the raw-barrier counted-vmcnt one.
 template <typename T, typename V8>
-void launch_tn_colsum(const torch::Tensor& A, const torch::Tensor& B,
-                      torch::Tensor& P, torch::Tensor& C, torch::Tensor& CS,
-                      long M, long N, long K, int tiles2, int sm,
-                      hipStream_t stream) {
+void launch_tn_v2(const torch::Tensor& A, const torch::Tensor& B,
+                  torch::Tensor& P, torch::Tensor& C, torch::Tensor& CS,
+                  long M, long N, long K, int tiles2, int sm, bool colsum,
+                  bool sync, hipStream_t stream) {
   const int nwg2 = tiles2 * sm;
   const long NK = N * K;
   const int rblocks = (int)((NK / 4 + 255) / 256);
-  const int cblocks = (int)((N / 4 + 255) / 256);
-  if (getenv("PDNLP_TN_SYNC") == nullptr)
-    hipLaunchKernelGGL((gemm_tn_sk_kernel<T, V8, true, false, true>),
-                       dim3(nwg2), dim3(512), 0, stream,
-                       (const T*)A.data_ptr(), (const T*)B.data_ptr(),
-                       (float*)P.data_ptr(), M, N, K, (int)(K / 128), tiles2,
-                       sm, nwg2);
-  else
-    hipLaunchKernelGGL((gemm_tn_sk_kernel<T, V8, false, false, true>),
-                       dim3(nwg2), dim3(512), 0, stream,
-                       (const T*)A.data_ptr(), (const T*)B.data_ptr(),
-                       (float*)P.data_ptr(), M, N, K, (int)(K / 128), tiles2,
-                       sm, nwg2);
-  hipLaunchKernelGGL((reduce_partials_colsum_kernel<T>),
-                     dim3(rblocks + cblocks), dim3(256), 0, stream,
-                     (const float*)P.data_ptr(), (T*)C.data_ptr(),
-                     (T*)CS.data_ptr(), NK, N, sm, rblocks);
+  auto kernel =
+      colsum ? (sync ? gemm_tn_sk_kernel<T, V8, false, true>
+                     : gemm_tn_sk_kernel<T, V8, true, true>)
+             : (sync ? gemm_tn_sk_kernel<T, V8, false, false>
+                     : gemm_tn_sk_kernel<T, V8, true, false>);
+  hipLaunchKernelGGL(kernel, dim3(nwg2), dim3(512), 0, stream,
+                     (const T*)A.data_ptr(), (const T*)B.data_ptr(),
+                     (float*)P.data_ptr(), M, N, K, (int)(K / 128), tiles2,
+                     sm, nwg2);
+  if (colsum) {
+    const int cblocks = (int)((N / 4 + 255) / 256);
+    hipLaunchKernelGGL((reduce_partials_colsum_kernel<T>),
+                       dim3(rblocks + cblocks), dim3(256), 0, stream,
+                       (const float*)P.data_ptr(), (T*)C.data_ptr(),
+                       (T*)CS.data_ptr(), NK, N, sm, rblocks);
+  } else {
+    hipLaunchKernelGGL((reduce_partials_kernel<T>), dim3(rblocks), dim3(256),
+                       0, stream, (const float*)P.data_ptr(),
+                       (T*)C.data_ptr(), NK, sm);
+  }
+}
+
+// single-pass 64x64 launches (off the 128 grid, or PDNLP_TN_V1)
+template <typename T, typename V8>
+void launch_tn_64(const torch::Tensor& A, const torch::Tensor& B,
+                  torch::Tensor& C, long M, long N, long K,
+                  hipStream_t stream) {
+  const int tiles_k = (int)((K + BT - 1) / BT);
+  const int nwg = (int)((N + BT - 1) / BT) * tiles_k;
+  const bool w8 = getenv("PDNLP_TN_W4") == nullptr;  // 8 waves default
+  auto kernel = w8 ? gemm_tn_w8_kernel<T, V8> : gemm_tn_kernel<T, V8>;
+  hipLaunchKernelGGL(kernel, dim3(nwg), dim3(w8 ? 512 : NTHREADS), 0, stream,
+                     (const T*)A.data_ptr(), (const T*)B.data_ptr(),
+                     (T*)C.data_ptr(), M, N, K, tiles_k, nwg);
 }
 
 }  // namespace
 
-// C = A^T @ B for row-major A [M, N], B [M, K]; returns C [N, K] in A's
-// dtype (fp32 accumulation). Requires M % 64 == 0, N % 16 == 0, K % 16 == 0.
-torch::Tensor gemm_tn(torch::Tensor A, torch::Tensor B) {
+torch::Tensor col_sum(torch::Tensor x);
+
+namespace {
+
+// {C, CS}: C = A^T @ B; with `colsum`, CS[n] = sum_m A[m, n] (else undefined).
+// Both entry points run this, so C cannot differ between them.
+std::pair<torch::Tensor, torch::Tensor> tn_impl(const torch::Tensor& A,
+                                                const torch::Tensor& B,
+                                                bool colsum) {
   TORCH_CHECK(A.is_cuda() && A.is_contiguous() && B.is_contiguous());
   TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.size(0) == B.size(0));
   const long M = A.size(0), N = A.size(1), K = B.size(1);
@@ -603,138 +459,52 @@ torch::Tensor gemm_tn(torch::Tensor A, torch::Tensor B) {
   // contraction rows clamped — partial-width column tiles would read OOB
   TORCH_CHECK(N % 64 == 0 && K % 64 == 0,
               "gemm_tn: N and K must be multiples of 64");
+  const bool bf16 = A.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(bf16 || A.scalar_type() == torch::kHalf,
+              "gemm_tn: bf16/fp16 only");
+  TORCH_CHECK(A.scalar_type() == B.scalar_type(),
+              "gemm_tn: A and B dtypes differ");
   auto C = torch::empty({N, K}, A.options());
+  torch::Tensor CS;
   auto stream = at::hip::getCurrentHIPStream();
-  const bool serial = getenv("PDNLP_TN_SERIAL") != nullptr;
-  const bool w8 = getenv("PDNLP_TN_W4") == nullptr;  // 8 waves default
-  // v2 (default): 128x128 tiles + split-M + fp32 partials when on-grid
-  const bool v2_ok = getenv("PDNLP_TN_V1") == nullptr && !serial
-      && N % 128 == 0 && K % 128 == 0
-      && (A.scalar_type() == torch::kBFloat16
-          || A.scalar_type() == torch::kHalf);
-  if (v2_ok) {
-    const int tiles2 = (int)((N / 128) * (K / 128));
-    const int sm = tn_v2_split(M, tiles2);
-    const int nwg2 = tiles2 * sm;
-    auto P = torch::empty({sm, N, K},
-                          A.options().dtype(torch::kFloat32));
-    const long NK = N * K;
-    const int rblocks = (int)((NK / 4 + 255) / 256);
-    // raw-barrier counted-vmcnt schedule is DEFAULT (step-level +2.5-3%
-    // measured on two boxes: gpurun_out/b_rb*.log); PDNLP_TN_SYNC reverts
-    const bool rb = getenv("PDNLP_TN_SYNC") == nullptr;
-    // TIMING PROBE (numerics INVALID — races by construction): bounds what
-    // a perfect barrier-free pipeline could buy on this structure
-    const bool probe = getenv("PDNLP_TN_PROBE") != nullptr;
-    if (A.scalar_type() == torch::kBFloat16) {
-      if (probe)
-        hipLaunchKernelGGL(
-            (gemm_tn_sk_kernel<__hip_bfloat16, bf16x8, true, true>),
-            dim3(nwg2), dim3(512), 0, stream,
-            (const __hip_bfloat16*)A.data_ptr(),
-            (const __hip_bfloat16*)B.data_ptr(), (float*)P.data_ptr(),
-            M, N, K, (int)(K / 128), tiles2, sm, nwg2);
-      else if (rb)
-        hipLaunchKernelGGL((gemm_tn_sk_kernel<__hip_bfloat16, bf16x8, true>),
-                           dim3(nwg2), dim3(512), 0, stream,
-                           (const __hip_bfloat16*)A.data_ptr(),
-                           (const __hip_bfloat16*)B.data_ptr(),
-                           (float*)P.data_ptr(), M, N, K,
-                           (int)(K / 128), tiles2, sm, nwg2);
-      else
-        hipLaunchKernelGGL((gemm_tn_sk_kernel<__hip_bfloat16, bf16x8>),
-                           dim3(nwg2), dim3(512), 0, stream,
-                           (const __hip_bfloat16*)A.data_ptr(),
-                           (const __hip_bfloat16*)B.data_ptr(),
-                           (float*)P.data_ptr(), M, N, K,
-                           (int)(K / 128), tiles2, sm, nwg2);
-      hipLaunchKernelGGL((reduce_partials_kernel<__hip_bfloat16>),
-                         dim3(rblocks), dim3(256), 0, stream,
-                         (const float*)P.data_ptr(),
-                         (__hip_bfloat16*)C.data_ptr(), NK, sm);
-    } else {
-      hipLaunchKernelGGL((gemm_tn_sk_kernel<__half, f16x8>),
-                         dim3(nwg2), dim3(512), 0, stream,
-                         (const __half*)A.data_ptr(),
-                         (const __half*)B.data_ptr(),
-                         (float*)P.data_ptr(), M, N, K,
-                         (int)(K / 128), tiles2, sm, nwg2);
-      hipLaunchKernelGGL((reduce_partials_kernel<__half>),
-                         dim3(rblocks), dim3(256), 0, stream,
-                         (const float*)P.data_ptr(),
-                         (__half*)C.data_ptr(), NK, sm);
-    }
-    return C;
+  if (!tn_v2_ok(N, K)) {
+    if (bf16) launch_tn_64<__hip_bfloat16, bf16x8>(A, B, C, M, N, K, stream);
+    else launch_tn_64<__half, f16x8>(A, B, C, M, N, K, stream);
+    if (colsum) CS = col_sum(A);
+    return {C, CS};
   }
-  const int tiles_n = (int)((N + BT - 1) / BT);
-  const int tiles_k = (int)((K + BT - 1) / BT);
-  const int nwg = tiles_n * tiles_k;
-  if (A.scalar_type() == torch::kBFloat16) {
-    if (serial)
-      hipLaunchKernelGGL((gemm_tn_kernel<__hip_bfloat16, bf16x8, false>),
-                         dim3(nwg), dim3(NTHREADS), 0, stream,
-                         (const __hip_bfloat16*)A.data_ptr(),
-                         (const __hip_bfloat16*)B.data_ptr(),
-                         (__hip_bfloat16*)C.data_ptr(), M, N, K, tiles_k, nwg);
-    else if (w8)
-      hipLaunchKernelGGL((gemm_tn_w8_kernel<__hip_bfloat16, bf16x8>),
-                         dim3(nwg), dim3(512), 0, stream,
-                         (const __hip_bfloat16*)A.data_ptr(),
-                         (const __hip_bfloat16*)B.data_ptr(),
-                         (__hip_bfloat16*)C.data_ptr(), M, N, K, tiles_k, nwg);
-    else
-      hipLaunchKernelGGL((gemm_tn_kernel<__hip_bfloat16, bf16x8, true>),
-                         dim3(nwg), dim3(NTHREADS), 0, stream,
-                         (const __hip_bfloat16*)A.data_ptr(),
-                         (const __hip_bfloat16*)B.data_ptr(),
-                         (__hip_bfloat16*)C.data_ptr(), M, N, K, tiles_k, nwg);
-  } else if (A.scalar_type() == torch::kHalf) {
-    if (w8)
-      hipLaunchKernelGGL((gemm_tn_w8_kernel<__half, f16x8>), dim3(nwg),
-                         dim3(512), 0, stream,
-                         (const __half*)A.data_ptr(),
-                         (const __half*)B.data_ptr(),
-                         (__half*)C.data_ptr(), M, N, K, tiles_k, nwg);
-    else
-      hipLaunchKernelGGL((gemm_tn_kernel<__half, f16x8, true>), dim3(nwg),
-                         dim3(NTHREADS), 0, stream,
-                         (const __half*)A.data_ptr(), (const __half*)B.data_ptr(),
-                         (__half*)C.data_ptr(), M, N, K, tiles_k, nwg);
-  } else {
-    TORCH_CHECK(false, "gemm_tn: bf16/fp16 only");
-  }
-  return C;
+  const int tiles2 = (int)((N / 128) * (K / 128));
+  const int sm = tn_v2_split(M, tiles2);
+  // dW partials [sm][N][K], then (colsum) the column-sum slices [sm][N]
+  auto P = torch::empty({(long)sm * (N * K + (colsum ? N : 0))},
+                        A.options().dtype(torch::kFloat32));
+  if (colsum) CS = torch::empty({N}, A.options());
+  // raw-barrier counted-vmcnt schedule is the default (step-level +2.5-3%
+  // measured on two boxes), PDNLP_TN_SYNC reverts — except that plain fp16
+  // has only ever run the synchronous one (open inconsistency)
+  const bool sync = getenv("PDNLP_TN_SYNC") != nullptr || (!colsum && !bf16);
+  if (bf16)
+    launch_tn_v2<__hip_bfloat16, bf16x8>(A, B, P, C, CS, M, N, K, tiles2, sm,
+                                         colsum, sync, stream);
+  else
+    launch_tn_v2<__half, f16x8>(A, B, P, C, CS, M, N, K, tiles2, sm, colsum,
+                                sync, stream);
+  return {C, CS};
 }
 
-torch::Tensor col_sum(torch::Tensor x);
+}  // namespace
+
+// C = A^T @ B for row-major A [M, N], B [M, K]; returns C [N, K] in A's
+// dtype (fp32 accumulation). Requires M, N and K to be multiples of 64.
+torch::Tensor gemm_tn(torch::Tensor A, torch::Tensor B) {
+  return tn_impl(A, B, false).first;
+}
 
 // {C, colsum} with C = gemm_tn(A, B) (bit-identical) and colsum[n] =
 // sum_m A[m, n] in A's dtype — the dW/db pair of a biased projection from
 // one pass over dY. On the v2 grid the sums ride along in the GEMM (see
-// COLSUM above); every other path computes C as gemm_tn does and takes the
-// sums from col_sum.
+// COLSUM above); the 64x64 path takes them from col_sum.
 std::vector<torch::Tensor> gemm_tn_colsum(torch::Tensor A, torch::Tensor B) {
-  TORCH_CHECK(A.is_cuda() && A.is_contiguous() && B.is_contiguous());
-  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.size(0) == B.size(0));
-  const long M = A.size(0), N = A.size(1), K = B.size(1);
-  if (!tn_v2_ok(A, N, K) || getenv("PDNLP_TN_PROBE") != nullptr)
-    return {gemm_tn(A, B), col_sum(A)};
-  TORCH_CHECK(M % BC == 0, "gemm_tn: M must be a multiple of 64");
-  TORCH_CHECK(A.scalar_type() == B.scalar_type(),
-              "gemm_tn_colsum: A and B dtypes differ");
-  auto C = torch::empty({N, K}, A.options());
-  auto CS = torch::empty({N}, A.options());
-  const int tiles2 = (int)((N / 128) * (K / 128));
-  const int sm = tn_v2_split(M, tiles2);
-  // dW partials [sm][N][K], then the column-sum slices [sm][N]
-  auto P = torch::empty({(long)sm * (N * K + N)},
-                        A.options().dtype(torch::kFloat32));
-  auto stream = at::hip::getCurrentHIPStream();
-  if (A.scalar_type() == torch::kBFloat16)
-    launch_tn_colsum<__hip_bfloat16, bf16x8>(A, B, P, C, CS, M, N, K, tiles2,
-                                             sm, stream);
-  else
-    launch_tn_colsum<__half, f16x8>(A, B, P, C, CS, M, N, K, tiles2, sm,
-                                    stream);
-  return {C, CS};
+  auto r = tn_impl(A, B, true);
+  return {r.first, r.second};
 }

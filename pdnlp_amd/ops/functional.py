@@ -9,6 +9,7 @@ tested against). Kernel inventory mirrors SURVEY.md §2.3 K1-K16.
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional
 
 import torch
@@ -83,7 +84,7 @@ def embedding_layernorm(input_ids, token_type_ids, position_ids,
 
 # --------------------------------------------------------------------------
 # Linear (K2/K6/K7/K8 GEMMs). HIP MFMA GEMM for the hot shapes; the
-# backward dGEMMs (plain, no fusion) go through rocBLAS via torch.matmul.
+# backward dGEMMs follow one policy (_dx / _dw_db below).
 # --------------------------------------------------------------------------
 
 class _DwStream:
@@ -107,7 +108,6 @@ class _DwStream:
         self.stream = None
 
     def enabled(self) -> bool:
-        import os
         return (os.environ.get("PDNLP_DW_STREAM", "0") == "1"
                 and torch.cuda.is_available())
 
@@ -140,7 +140,6 @@ def _dgemm_mode() -> str:
     r02_nn256_sweep.txt). dW is first-party on every measured shape.
     "hip": force first-party for ALL dGEMMs (pure-rocprof-hand-written).
     "blas": force torch.matmul (rocBLAS/hipBLASLt) for A/B sweeps."""
-    import os
     return os.environ.get("PDNLP_DGEMM", "auto")
 
 
@@ -153,22 +152,10 @@ def _nn_blas_faster(m: int, k: int) -> bool:
     return False
 
 
-def _nn_shape_ok(dy2, w) -> bool:
-    return (dy2.dtype in (torch.bfloat16, torch.float16)
-            and dy2.shape[1] % 64 == 0 and w.shape[1] % 64 == 0)
-
-
 def _tn_shape_ok(dy2, x2) -> bool:
     return (dy2.dtype in (torch.bfloat16, torch.float16)
             and dy2.shape[0] % 64 == 0 and dy2.shape[1] % 64 == 0
             and x2.shape[1] % 64 == 0)
-
-
-def _tn_colsum_ok(dy2, x2, mode) -> bool:
-    """True when dW and the bias gradient come from ONE gemm_tn_colsum call
-    (the column sum of dY rides along in the first-party dW GEMM)."""
-    return (mode in ("hip", "auto") and _tn_shape_ok(dy2, x2)
-            and getattr(ext(), "gemm_tn_colsum", None) is not None)
 
 
 def _bias_grad(dy2):
@@ -176,6 +163,78 @@ def _bias_grad(dy2):
             and dy2.dtype != torch.float32:
         return ext().col_sum(dy2)
     return dy2.sum(0)
+
+
+# The backward-GEMM policy of every HIP linear lives in _dx and _dw_db. The
+# forward gate (_gemm_shape_ok) already guarantees what the NN kernel needs
+# (bf16/fp16, in- and out-features multiples of 64), so _dx checks no shape.
+
+def _dx(dy2, w, dpass=None):
+    """dX = dy2 @ w (+ dpass, the gradient of a forked pass-through input):
+    first-party MFMA NN unless the policy (_dgemm_mode / _nn_blas_faster)
+    hands the shape to rocBLAS."""
+    mode = _dgemm_mode()
+    hip = (mode == "hip"
+           or (mode == "auto"
+               and not _nn_blas_faster(dy2.shape[0], w.shape[1])))
+    if dpass is None:
+        return ext().gemm_nn(dy2, w) if hip else dy2 @ w
+    if not hip:
+        # vendor-GEMM shapes: addmm fuses the residual-grad add too
+        return torch.addmm(dpass.reshape(-1, dpass.shape[-1]), dy2, w)
+    if dpass.is_contiguous():
+        # the add rides in the dX GEMM's epilogue
+        return ext().gemm_nn_add(dy2, w, dpass.view(-1, dpass.shape[-1]))
+    return ext().gemm_nn(dy2, w) + dpass.reshape(-1, dpass.shape[-1])
+
+
+def _dw_db(dy2, x2, need_db, side_stream=False):
+    """(dW, db) = (dy2^T @ x2, column sums of dy2 or None). On the
+    first-party grid a needed db comes out of the dW GEMM itself
+    (gemm_tn_colsum); elsewhere from _bias_grad. ``side_stream`` lets
+    PDNLP_DW_STREAM=1 move dW off the backward critical path."""
+    db = None
+    if side_stream and dw_stream.enabled():
+        s = dw_stream.get()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            dw = dy2.t() @ x2
+        dy2.record_stream(s)
+        x2.record_stream(s)
+        dw.record_stream(torch.cuda.current_stream())
+    elif _dgemm_mode() in ("hip", "auto") and _tn_shape_ok(dy2, x2):
+        if need_db:
+            dw, db = ext().gemm_tn_colsum(dy2, x2)  # dW + db in one pass
+        else:
+            dw = ext().gemm_tn(dy2, x2)             # first-party MFMA TN
+    else:
+        dw = dy2.t() @ x2                           # rocBLAS TN
+    if need_db and db is None:
+        db = _bias_grad(dy2)
+    return dw, db
+
+
+def _linear_fwd(ctx, x, w, b, act):
+    x2 = x.contiguous().view(-1, x.shape[-1])
+    y, pre = ext().gemm_nt_fwd(x2, w, b if b is not None else torch.Tensor(),
+                               act)
+    ctx.save_for_backward(x2, w, pre if act != "none" else torch.Tensor())
+    ctx.act = act
+    ctx.in_shape = x.shape
+    return y.view(*x.shape[:-1], w.shape[0])
+
+
+def _linear_bwd(ctx, dy, need_db, dpass=None, side_stream=False):
+    """Activation backward, then the two dGEMMs: (dx, dw, db)."""
+    x2, w, pre = ctx.saved_tensors
+    dy2 = dy.contiguous().view(-1, dy.shape[-1])
+    if ctx.act == "gelu":
+        dy2 = ext().gelu_bwd(dy2, pre)
+    elif ctx.act == "tanh":
+        dy2 = ext().tanh_bwd(dy2, pre)
+    dx = _dx(dy2, w, dpass)
+    dw, db = _dw_db(dy2, x2, need_db, side_stream)
+    return dx.view(ctx.in_shape), dw, db
 
 
 class _LinearHipFn(torch.autograd.Function):
@@ -186,49 +245,13 @@ class _LinearHipFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b, act):
-        x2 = x.contiguous().view(-1, x.shape[-1])
-        y, pre = ext().gemm_nt_fwd(x2, w, b if b is not None else torch.Tensor(), act)
-        ctx.save_for_backward(x2, w, pre if act != "none" else torch.Tensor())
-        ctx.act = act
         ctx.has_bias = b is not None
-        ctx.in_shape = x.shape
-        return y.view(*x.shape[:-1], w.shape[0])
+        return _linear_fwd(ctx, x, w, b, act)
 
     @staticmethod
     def backward(ctx, dy):
-        x2, w, pre = ctx.saved_tensors
-        dy2 = dy.contiguous().view(-1, dy.shape[-1])
-        db = None
-        if ctx.act == "gelu":
-            dy2 = ext().gelu_bwd(dy2, pre)
-        elif ctx.act == "tanh":
-            dy2 = ext().tanh_bwd(dy2, pre)
-        mode = _dgemm_mode()
-        hip_dx = (mode == "hip"
-                  or (mode == "auto"
-                      and not _nn_blas_faster(dy2.shape[0], w.shape[1])))
-        hip_dw = mode in ("hip", "auto")
-        if hip_dx and _nn_shape_ok(dy2, w):
-            dx = ext().gemm_nn(dy2, w)    # first-party MFMA NN
-        else:
-            dx = dy2 @ w                  # rocBLAS NN
-        if dw_stream.enabled():
-            s = dw_stream.get()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                dw = dy2.t() @ x2         # off the backward critical path
-            dy2.record_stream(s)
-            x2.record_stream(s)
-            dw.record_stream(torch.cuda.current_stream())
-        elif ctx.has_bias and _tn_colsum_ok(dy2, x2, mode):
-            dw, db = ext().gemm_tn_colsum(dy2, x2)  # dW + db in one pass
-        elif hip_dw and _tn_shape_ok(dy2, x2):
-            dw = ext().gemm_tn(dy2, x2)   # first-party MFMA TN
-        else:
-            dw = dy2.t() @ x2             # rocBLAS TN
-        if ctx.has_bias and db is None:
-            db = _bias_grad(dy2)
-        return dx.view(ctx.in_shape), dw, db, None
+        # the only linear whose dW may go to the PDNLP_DW_STREAM side stream
+        return (*_linear_bwd(ctx, dy, ctx.has_bias, side_stream=True), None)
 
 
 class _LinearDeferredBiasHipFn(torch.autograd.Function):
@@ -242,35 +265,11 @@ class _LinearDeferredBiasHipFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b):
-        x2 = x.contiguous().view(-1, x.shape[-1])
-        y, _ = ext().gemm_nt_fwd(x2, w, torch.Tensor(), "none")
-        ctx.save_for_backward(x2, w)
-        ctx.in_shape = x.shape
-        return y.view(*x.shape[:-1], w.shape[0])
+        return _linear_fwd(ctx, x, w, None, "none")
 
     @staticmethod
     def backward(ctx, dy):
-        x2, w = ctx.saved_tensors
-        dy2 = dy.contiguous().view(-1, dy.shape[-1])
-        mode = _dgemm_mode()
-        hip_dx = (mode == "hip"
-                  or (mode == "auto"
-                      and not _nn_blas_faster(dy2.shape[0], w.shape[1])))
-        if hip_dx and _nn_shape_ok(dy2, w):
-            dx = ext().gemm_nn(dy2, w)
-        else:
-            dx = dy2 @ w
-        need_db = ctx.needs_input_grad[2]
-        db = None
-        if need_db and _tn_colsum_ok(dy2, x2, mode):
-            dw, db = ext().gemm_tn_colsum(dy2, x2)
-        elif mode in ("hip", "auto") and _tn_shape_ok(dy2, x2):
-            dw = ext().gemm_tn(dy2, x2)
-        else:
-            dw = dy2.t() @ x2
-        if need_db and db is None:
-            db = _bias_grad(dy2)
-        return dx.view(ctx.in_shape), dw, db
+        return _linear_bwd(ctx, dy, ctx.needs_input_grad[2])
 
 
 class _LinearForkHipFn(torch.autograd.Function):
@@ -286,52 +285,12 @@ class _LinearForkHipFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b, act):
-        x2 = x.contiguous().view(-1, x.shape[-1])
-        y, pre = ext().gemm_nt_fwd(x2, w,
-                                   b if b is not None else torch.Tensor(),
-                                   act)
-        ctx.save_for_backward(x2, w, pre if act != "none" else torch.Tensor())
-        ctx.act = act
         ctx.has_bias = b is not None
-        ctx.in_shape = x.shape
-        return y.view(*x.shape[:-1], w.shape[0]), x
+        return _linear_fwd(ctx, x, w, b, act), x
 
     @staticmethod
     def backward(ctx, dy, dpass):
-        x2, w, pre = ctx.saved_tensors
-        dy2 = dy.contiguous().view(-1, dy.shape[-1])
-        if ctx.act == "gelu":
-            dy2 = ext().gelu_bwd(dy2, pre)
-        elif ctx.act == "tanh":
-            dy2 = ext().tanh_bwd(dy2, pre)
-        mode = _dgemm_mode()
-        hip_dx = (mode == "hip"
-                  or (mode == "auto"
-                      and not _nn_blas_faster(dy2.shape[0], w.shape[1])))
-        if dpass is not None and hip_dx and _nn_shape_ok(dy2, w) \
-                and dpass.is_contiguous():
-            dx = ext().gemm_nn_add(dy2, w,
-                                   dpass.view(-1, dpass.shape[-1]))
-        elif dpass is not None and not (hip_dx and _nn_shape_ok(dy2, w)):
-            # vendor-GEMM shapes: addmm fuses the residual-grad add too
-            dx = torch.addmm(dpass.reshape(-1, dpass.shape[-1]), dy2, w)
-        else:
-            if hip_dx and _nn_shape_ok(dy2, w):
-                dx = ext().gemm_nn(dy2, w)
-            else:
-                dx = dy2 @ w
-            if dpass is not None:
-                dx = dx + dpass.reshape(-1, dpass.shape[-1])
-        db = None
-        if ctx.has_bias and _tn_colsum_ok(dy2, x2, mode):
-            dw, db = ext().gemm_tn_colsum(dy2, x2)  # dW + db in one pass
-        elif mode in ("hip", "auto") and _tn_shape_ok(dy2, x2):
-            dw = ext().gemm_tn(dy2, x2)
-        else:
-            dw = dy2.t() @ x2
-        if ctx.has_bias and db is None:
-            db = _bias_grad(dy2)
-        return dx.view(ctx.in_shape), dw, db, None
+        return (*_linear_bwd(ctx, dy, ctx.has_bias, dpass=dpass), None)
 
 
 def linear_fork(x: torch.Tensor, w: torch.Tensor,
@@ -339,8 +298,7 @@ def linear_fork(x: torch.Tensor, w: torch.Tensor,
     """Returns ``(linear(x, w, b, act), x)`` — use the second output as the
     residual stream so the fan-in add fuses into the dX GEMM (HIP); on CPU
     this is exactly ``(linear(...), x)`` with autograd doing the add."""
-    if hip_enabled(x) and getattr(ext(), "gemm_nn_add", None) is not None \
-            and _gemm_shape_ok(x, w):
+    if hip_enabled(x) and _gemm_shape_ok(x, w):
         return _LinearForkHipFn.apply(x, w, b, act)
     return linear(x, w, b, act), x
 
@@ -375,16 +333,13 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
     PDNLP_FWD=blas routes plain (no-activation) projections through
     F.linear/hipBLASLt for A/B sweeps; activations always stay on the
     fused first-party kernel (unfusing them costs a full HBM round trip)."""
-    import os
     if os.environ.get("PDNLP_FWD") == "blas" and act == "none":
         return F.linear(x, w, b)
-    if hip_enabled(x) and getattr(ext(), "gemm_nt_fwd", None) is not None \
-            and _gemm_shape_ok(x, w):
+    if hip_enabled(x) and _gemm_shape_ok(x, w):
         return _LinearHipFn.apply(x, w, b, act)
     if hip_enabled(x) and act == "none" \
             and w.shape[0] in (1, 2, 4, 6, 8, 16) \
-            and x.dtype in (torch.bfloat16, torch.float16) \
-            and getattr(ext(), "skinny_linear_fwd", None) is not None:
+            and x.dtype in (torch.bfloat16, torch.float16):
         return _SkinnyLinearFn.apply(x, w, b)
     y = F.linear(x, w, b)
     if act == "gelu":
@@ -523,8 +478,7 @@ def attention_packed(qkv: torch.Tensor, mask: Optional[torch.Tensor],
     H = H3 // 3
     hd = H // num_heads
     p_eff = float(dropout_p if training else 0.0)
-    if hip_enabled(qkv) and getattr(ext(), "flash_attn_qkv_fwd", None) is not None \
-            and hd == 64 and S % 64 == 0 \
+    if hip_enabled(qkv) and hd == 64 and S % 64 == 0 \
             and qkv.dtype in (torch.bfloat16, torch.float16):
         scale = 1.0 / math.sqrt(hd)
         return _FlashAttnQKVFn.apply(
@@ -577,8 +531,14 @@ def reseed_dropout(seed=None) -> None:
 
 
 class _BiasDropResLNFn(torch.autograd.Function):
+    """``need_dbias=False``: the bias has no gradient path here — the
+    backward skips the bias column sum (one of the three input streams of
+    its second pass) and the producing projection returns that gradient
+    instead (_LinearDeferredBiasHipFn)."""
+
     @staticmethod
-    def forward(ctx, y, bias, residual, ln_w, ln_b, p, training, eps):
+    def forward(ctx, y, bias, residual, ln_w, ln_b, p, training, eps,
+                need_dbias):
         p_eff = float(p if training else 0.0)
         if p_eff > 0.0:
             seed_buf, salt = _dropout_seed.get(y.device)
@@ -589,13 +549,19 @@ class _BiasDropResLNFn(torch.autograd.Function):
             p_eff, eps, seed_buf, salt)
         ctx.save_for_backward(xsum, mask, ln_w, mean, rstd)
         ctx.p = p_eff
+        ctx.need_dbias = need_dbias
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        xsum, mask, ln_w, mean, rstd = ctx.saved_tensors
-        dy, dbias, dres, dlnw, dlnb = ext().bias_dropout_residual_ln_bwd(
-            dout.contiguous(), xsum, mask, ln_w, mean, rstd, ctx.p)
+        args = (dout.contiguous(), *ctx.saved_tensors, ctx.p)
+        if ctx.need_dbias:
+            dy, dbias, dres, dlnw, dlnb = \
+                ext().bias_dropout_residual_ln_bwd(*args)
+        else:
+            dbias = None
+            dy, dres, dlnw, dlnb = \
+                ext().bias_dropout_residual_ln_bwd_nodb(*args)
         return dy, dbias, dres, dlnw, dlnb, None, None, None, None
 
 
@@ -607,40 +573,12 @@ def bias_dropout_residual_layernorm(
     attention-output and FFN-down projections."""
     if hip_enabled(y) and y.shape[-1] % 256 == 0 and y.shape[-1] <= 1024:
         return _BiasDropResLNFn.apply(y, bias, residual, ln_w, ln_b, p,
-                                      training, eps)
+                                      training, eps, True)
     h = y + bias
     if p > 0.0 and training:
         h = F.dropout(h, p=p, training=True)
     h = h + residual
     return F.layer_norm(h, (h.shape[-1],), ln_w, ln_b, eps)
-
-
-class _BiasDropResLNNoDbFn(torch.autograd.Function):
-    """_BiasDropResLNFn whose bias has no gradient path here: the backward
-    skips the bias column sum (one of the three input streams of its
-    second pass). The producing projection returns that gradient
-    (_LinearDeferredBiasHipFn)."""
-
-    @staticmethod
-    def forward(ctx, y, bias, residual, ln_w, ln_b, p, training, eps):
-        p_eff = float(p if training else 0.0)
-        if p_eff > 0.0:
-            seed_buf, salt = _dropout_seed.get(y.device)
-        else:
-            seed_buf, salt = torch.Tensor(), 0
-        out, xsum, mask, mean, rstd = ext().bias_dropout_residual_ln_fwd(
-            y.contiguous(), bias, residual.contiguous(), ln_w, ln_b,
-            p_eff, eps, seed_buf, salt)
-        ctx.save_for_backward(xsum, mask, ln_w, mean, rstd)
-        ctx.p = p_eff
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        xsum, mask, ln_w, mean, rstd = ctx.saved_tensors
-        dy, dres, dlnw, dlnb = ext().bias_dropout_residual_ln_bwd_nodb(
-            dout.contiguous(), xsum, mask, ln_w, mean, rstd, ctx.p)
-        return dy, None, dres, dlnw, dlnb, None, None, None
 
 
 def linear_bias_dropout_residual_layernorm(
@@ -655,21 +593,16 @@ def linear_bias_dropout_residual_layernorm(
     inside that GEMM (``gemm_tn_colsum``) and the epilogue's backward no
     longer sums dy for it. Everywhere else this is exactly
     ``bias_dropout_residual_layernorm(linear(x, w, None), b, ...)``."""
-    import os
     H = w.shape[0]
     rows = x.numel() // x.shape[-1]
     if hip_enabled(x) and H % 256 == 0 and H <= 1024 \
             and os.environ.get("PDNLP_FWD") != "blas" \
             and _dgemm_mode() in ("hip", "auto") \
             and not dw_stream.enabled() \
-            and getattr(ext(), "gemm_nt_fwd", None) is not None \
-            and getattr(ext(), "gemm_tn_colsum", None) is not None \
-            and getattr(ext(), "bias_dropout_residual_ln_bwd_nodb",
-                        None) is not None \
             and _gemm_shape_ok(x, w) and rows % 64 == 0:
         proj = _LinearDeferredBiasHipFn.apply(x, w, b)
-        return _BiasDropResLNNoDbFn.apply(
-            proj, b.detach(), residual, ln_w, ln_b, p, training, eps)
+        return _BiasDropResLNFn.apply(
+            proj, b.detach(), residual, ln_w, ln_b, p, training, eps, False)
     return bias_dropout_residual_layernorm(
         linear(x, w, None), b, residual, ln_w, ln_b, p, training, eps)
 
@@ -696,8 +629,7 @@ class _DropoutFn(torch.autograd.Function):
 
 
 def dropout(x: torch.Tensor, p: float, training: bool) -> torch.Tensor:
-    if p > 0.0 and training and hip_enabled(x) \
-            and getattr(ext(), "dropout_fwd", None) is not None:
+    if p > 0.0 and training and hip_enabled(x):
         return _DropoutFn.apply(x, float(p))
     return F.dropout(x, p=p, training=training)
 
@@ -721,6 +653,6 @@ class _CrossEntropyFn(torch.autograd.Function):
 
 
 def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-    if hip_enabled(logits) and getattr(ext(), "cross_entropy_fwd", None) is not None:
+    if hip_enabled(logits):
         return _CrossEntropyFn.apply(logits.float(), labels)
     return F.cross_entropy(logits.float(), labels)

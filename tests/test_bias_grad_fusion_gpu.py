@@ -179,7 +179,8 @@ def test_deferred_bias_composite_matches_composition(p):
     probe = Fops.linear_bias_dropout_residual_layernorm(
         case["x"].clone().requires_grad_(True), case["w"], case["b"],
         case["res"], case["lnw"], case["lnb"], 0.0, True, 1e-12)
-    assert "NoDb" in type(probe.grad_fn).__name__, type(probe.grad_fn)
+    assert "BiasDropResLN" in type(probe.grad_fn).__name__, type(probe.grad_fn)
+    assert probe.grad_fn.need_dbias is False
 
     salt0 = Fops._dropout_seed.salt
     res = {}

@@ -77,15 +77,16 @@ def main():
         v1 = fl / timeit(lambda: e.gemm_tn(A, B)) / 1e12
         os.environ.pop("PDNLP_TN_V1", None)
         auto = fl / timeit(lambda: e.gemm_tn(A, B)) / 1e12
-        os.environ["PDNLP_TN_RB"] = "1"
-        rb = fl / timeit(lambda: e.gemm_tn(A, B)) / 1e12
+        # auto runs the raw-barrier schedule; PDNLP_TN_SYNC reverts it
+        os.environ["PDNLP_TN_SYNC"] = "1"
+        sync = fl / timeit(lambda: e.gemm_tn(A, B)) / 1e12
         ok = torch.allclose(e.gemm_tn(A, B).float(),
                             (A.float().t() @ B.float()), rtol=6e-2, atol=6e-1)
-        os.environ.pop("PDNLP_TN_RB", None)
+        os.environ.pop("PDNLP_TN_SYNC", None)
         blas = fl / timeit(lambda: A.t() @ B) / 1e12
         row.sort(reverse=True)
         tops = " ".join(f"{n}:{v:.0f}" for v, n in row)
-        print(f"TN {M}x{N}x{K}: {tops} | auto {auto:.0f} rawbar {rb:.0f} "
+        print(f"TN {M}x{N}x{K}: {tops} | auto {auto:.0f} sync {sync:.0f} "
               f"(ok={ok}) v1 {v1:.0f} blas {blas:.0f}")
 
 
