@@ -152,8 +152,7 @@ __device__ __forceinline__ float qsum(float x) {
 // forward
 // ---------------------------------------------------------------------------
 
-template <typename T, typename V8, bool HAS_MASK, bool DROP, bool PRELOAD,
-          bool RAWBAR = false>
+template <typename T, typename V8, bool HAS_MASK, bool DROP, bool PRELOAD>
 __global__ __launch_bounds__(NTHREADS)
 void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
                    T* __restrict__ o, float* __restrict__ lse,
@@ -212,15 +211,6 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
     if (!PRELOAD && t + 1 < nt) {
       stage64<T>(kbase, ld, (long)(t + 1) * 64, S, k_lds[cur ^ 1]);
       stage64<T>(vbase, ld, (long)(t + 1) * 64, S, v_lds[cur ^ 1]);
-    }
-    if (RAWBAR && !PRELOAD) {
-      // counted wait: tile t+1's 4 glds stay in flight across the barrier
-      // and the whole compute of tile t (see gemm_tn.hip note)
-      if (t + 1 < nt)
-        asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
     }
     f32x4 acc_s[4] = {};
 #pragma unroll
@@ -292,13 +282,8 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
         acc_o[jd] = mfma16<V8>(a, bv[jd], acc_o[jd]);
     }
     if (!PRELOAD) {
-      if (RAWBAR) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
     }
     cur ^= 1;
   }
@@ -321,8 +306,7 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
 // backward dQ: grid over 64-row blocks; recompute P from lse, stream K/V
 // ---------------------------------------------------------------------------
 
-template <typename T, typename V8, bool HAS_MASK, bool DROP, bool PRELOAD,
-          bool RAWBAR = false>
+template <typename T, typename V8, bool HAS_MASK, bool DROP, bool PRELOAD>
 __global__ __launch_bounds__(NTHREADS)
 void fa_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
                       const T* __restrict__ o, const float* __restrict__ lse,
@@ -421,13 +405,6 @@ void fa_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
       stage64<T>(kbase, ld, (long)(t + 1) * 64, S, k_lds[cur ^ 1]);
       stage64<T>(vbase, ld, (long)(t + 1) * 64, S, v_lds[cur ^ 1]);
     }
-    if (RAWBAR && !PRELOAD) {
-      if (t + 1 < nt)
-        asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
     f32x4 acc_s[4] = {}, acc_dp[4] = {};
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
@@ -481,13 +458,8 @@ void fa_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
         acc_dq[jd] = mfma16<V8>(a, bk[jd], acc_dq[jd]);
     }
     if (!PRELOAD) {
-      if (RAWBAR) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
     }
     cur ^= 1;
   }
@@ -506,8 +478,7 @@ void fa_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
 // backward dK/dV: grid over 64-key blocks; S^T = K@Q^T so all GEMMs are A@B^T
 // ---------------------------------------------------------------------------
 
-template <typename T, typename V8, bool HAS_MASK, bool DROP, bool PRELOAD,
-          bool RAWBAR = false>
+template <typename T, typename V8, bool HAS_MASK, bool DROP, bool PRELOAD>
 __global__ __launch_bounds__(NTHREADS)
 void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
                        const T* __restrict__ /*o: consumed by the dQ pass*/,
@@ -578,13 +549,6 @@ void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
     if (!PRELOAD && t + 1 < nt) {
       stage64<T>(qbase, ld, (long)(t + 1) * 64, S, q_lds[cur ^ 1]);
       stage64<T>(dobase, H, (long)(t + 1) * 64, S, do_lds[cur ^ 1]);
-    }
-    if (RAWBAR && !PRELOAD) {
-      if (t + 1 < nt)
-        asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
     }
     // S^T = K @ Q^T and dP^T = V @ dO^T on this 64-query tile
     f32x4 acc_st[4] = {}, acc_dpt[4] = {};
@@ -676,13 +640,8 @@ void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
         acc_dk[jd] = mfma16<V8>(a, bq[jd], acc_dk[jd]);
     }
     if (!PRELOAD) {
-      if (RAWBAR) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
     }
     cur ^= 1;
   }
@@ -727,8 +686,8 @@ static void check_fa_args(const torch::Tensor& qkv, const torch::Tensor& mask,
 
 // launch macros live at file scope (a #define cannot appear inside a macro
 // argument — DISPATCH_FLOAT_TYPES takes the body as one)
-#define FA_FWD_L(PL, RB)                                                       \
-  hipLaunchKernelGGL((fa_fwd_kernel<scalar_t, V8, HM, DR, PL, RB>), grid,      \
+#define FA_FWD_L(PL)                                                           \
+  hipLaunchKernelGGL((fa_fwd_kernel<scalar_t, V8, HM, DR, PL>), grid,          \
                      dim3(NTHREADS), 0, stream,                                \
                      (const scalar_t*)qkv.data_ptr(),                          \
                      has_mask ? (const scalar_t*)mask.data_ptr() : nullptr,    \
@@ -738,13 +697,12 @@ static void check_fa_args(const torch::Tensor& qkv, const torch::Tensor& mask,
 #define FA_FWD(HMV, DRV)                                                       \
   do {                                                                         \
     constexpr bool HM = HMV, DR = DRV;                                         \
-    if (S <= 128) FA_FWD_L(true, false);                                       \
-    else if (fa_rb) FA_FWD_L(false, true);                                     \
-    else FA_FWD_L(false, false);                                               \
+    if (S <= 128) FA_FWD_L(true);                                              \
+    else FA_FWD_L(false);                                                      \
   } while (0)
 
-#define FA_BWD_L(KERN, PL, RB)                                                 \
-  hipLaunchKernelGGL((KERN<scalar_t, V8, HM, DR, PL, RB>), grid,               \
+#define FA_BWD_L(KERN, PL)                                                     \
+  hipLaunchKernelGGL((KERN<scalar_t, V8, HM, DR, PL>), grid,                   \
                      dim3(NTHREADS), 0, stream,                                \
                      (const scalar_t*)dout.data_ptr(),                         \
                      (const scalar_t*)qkv.data_ptr(),                          \
@@ -758,9 +716,8 @@ static void check_fa_args(const torch::Tensor& qkv, const torch::Tensor& mask,
 #define FA_BWD(KERN, HMV, DRV)                                                 \
   do {                                                                         \
     constexpr bool HM = HMV, DR = DRV;                                         \
-    if (S <= 128) FA_BWD_L(KERN, true, false);                                 \
-    else if (fa_rb) FA_BWD_L(KERN, false, true);                               \
-    else FA_BWD_L(KERN, false, false);                                         \
+    if (S <= 128) FA_BWD_L(KERN, true);                                        \
+    else FA_BWD_L(KERN, false);                                                \
   } while (0)
 
 std::vector<torch::Tensor> flash_attn_qkv_fwd(torch::Tensor qkv,
@@ -779,7 +736,6 @@ std::vector<torch::Tensor> flash_attn_qkv_fwd(torch::Tensor qkv,
   auto lse = torch::empty({B * nh, S}, qkv.options().dtype(torch::kFloat));
   dim3 grid(S / 64, B * nh);
   auto stream = at::hip::getCurrentHIPStream();
-  const bool fa_rb = getenv("PDNLP_FA_RB") != nullptr;
   const auto* seed_ptr =
       drop ? (const unsigned long long*)seed_buf.data_ptr() : nullptr;
 
@@ -809,7 +765,6 @@ torch::Tensor flash_attn_qkv_bwd(torch::Tensor dout, torch::Tensor qkv,
   auto dqkv = torch::empty_like(qkv);
   auto dvec = torch::empty({B * nh, S}, qkv.options().dtype(torch::kFloat));
   auto stream = at::hip::getCurrentHIPStream();
-  const bool fa_rb = getenv("PDNLP_FA_RB") != nullptr;
   const auto* seed_ptr =
       drop ? (const unsigned long long*)seed_buf.data_ptr() : nullptr;
 

@@ -32,19 +32,16 @@ constexpr int BK = 64;   // contraction chunk
 
 // A (dY) uses the row-major image (stage_tile/read_frag), B (W) the tr-read
 // image (stage_tr/frag_tr*) of gemm_common.h.
-template <typename T, typename V8, int BM, int BN, int NW,
-          bool RAWBAR = false, bool ADDD = false>
+template <typename T, typename V8, int BM, int BN, int NW, bool ADDD>
 __global__ __launch_bounds__(NW * WAVE)
 void gemm_nn_kernel(const T* __restrict__ A, const T* __restrict__ B,
                     T* __restrict__ C, long M, long N, long K,
-                    int tiles_n, int nwg, const T* __restrict__ D = nullptr) {
+                    int tiles_n, int nwg, const T* __restrict__ D) {
   constexpr int WM = NW == 8 ? 2 : ((BM >= 128 || BN < 128) ? 2 : 1);
   constexpr int WN = NW / WM;
   constexpr int TM = BM / WM, TN = BN / WN;
   constexpr int RM = TM / 16, RN = TN / 16;
   constexpr int NGB = BN / 64;         // 64-col B groups
-  // glds wave-instructions per buffer (for the counted-vmcnt schedule)
-  constexpr int GLDS = BM / (8 * NW) + NGB * (8 / NW);
 
   const int wg = xcd_remap(blockIdx.x, nwg);
   const long tile_m = wg / tiles_n, tile_n = wg % tiles_n;
@@ -67,10 +64,8 @@ void gemm_nn_kernel(const T* __restrict__ A, const T* __restrict__ B,
 
   stage_tile<T, BM, NW>(A, N, m0, M, 0, lds_a[0]);
   stage_b(0, lds_b[0]);
-  if constexpr (!RAWBAR) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
 
   const int ntiles = (int)(N / BK);
   int cur = 0;
@@ -78,18 +73,6 @@ void gemm_nn_kernel(const T* __restrict__ A, const T* __restrict__ B,
     if (t + 1 < ntiles) {
       stage_tile<T, BM, NW>(A, N, m0, M, (long)(t + 1) * BK, lds_a[cur ^ 1]);
       stage_b((long)(t + 1) * BK, lds_b[cur ^ 1]);
-    }
-    if constexpr (RAWBAR) {
-      // counted wait: the GLDS loads just issued for buffer t+1 STAY IN
-      // FLIGHT across the barrier and the whole compute of tile t —
-      // __syncthreads() here would emit vmcnt(0) and drain them (the
-      // ~20% stall the guide's pipelining note describes)
-      if (t + 1 < ntiles)
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"i"(GLDS)
-                     : "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
     }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
@@ -118,13 +101,8 @@ void gemm_nn_kernel(const T* __restrict__ A, const T* __restrict__ B,
         }
       }
     }
-    if constexpr (RAWBAR) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
     cur ^= 1;
   }
 
@@ -150,118 +128,29 @@ void gemm_nn_kernel(const T* __restrict__ A, const T* __restrict__ B,
   }
 }
 
-// 256x128 tile (dynamic LDS: 2x(32KB A + 16KB B) = 96KB, 1 WG/CU) for the
-// deep-grid shapes where 128x128 trails hipBLASLt (K >= 1024 / M = 8192) —
-// at 1 block/CU the counted-vmcnt raw-barrier span is the load-hiding
-// mechanism (guide: the pipelining lever is regime-gated to ~1 block/CU).
-template <typename T, typename V8>
-__global__ __launch_bounds__(512)
-void gemm_nn_256_kernel(const T* __restrict__ A, const T* __restrict__ B,
-                        T* __restrict__ C, long M, long N, long K,
-                        int tiles_n, int nwg) {
-  constexpr int BM = 256, BN = 128, NW = 8;
-  constexpr int WM = 2, WN = 4;
-  constexpr int TM = BM / WM, TN = BN / WN;   // 128 x 32
-  constexpr int RM = TM / 16, RN = TN / 16;   // 8 x 2
-  constexpr int NGB = BN / 64;
-  constexpr int GLDS = BM / (8 * NW) + NGB * (8 / NW);  // 4 + 2 = 6
-
-  const int wg = xcd_remap(blockIdx.x, nwg);
-  const long tile_m = wg / tiles_n, tile_n = wg % tiles_n;
-  const long m0 = tile_m * BM, k0 = tile_n * BN;
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  auto lds_a = [&](int i) -> char* { return smem + i * (BM * 128); };
-  auto lds_b = [&](int i) -> char* {
-    return smem + 2 * (BM * 128) + i * (NGB * 8192);
-  };
-
-  const int wid = threadIdx.x >> 6;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wr = (wid / WN) * TM, wc = (wid % WN) * TN;
-
-  f32x4 acc[RM][RN] = {};
-
-  auto stage_b = [&](long n_base, char* lds) {
-#pragma unroll
-    for (int g = 0; g < NGB; ++g)
-      stage_tr<T, NW>(B, K, n_base, N, k0 + g * 64, lds + g * 8192);
-  };
-
-  stage_tile<T, BM, NW>(A, N, m0, M, 0, lds_a(0));
-  stage_b(0, lds_b(0));
-
-  const int ntiles = (int)(N / BK);
-  int cur = 0;
-  for (int t = 0; t < ntiles; ++t) {
-    if (t + 1 < ntiles) {
-      stage_tile<T, BM, NW>(A, N, m0, M, (long)(t + 1) * BK, lds_a(cur ^ 1));
-      stage_b((long)(t + 1) * BK, lds_b(cur ^ 1));
-      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"i"(GLDS) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      V8 a_frag[RM], b_frag[RN];
-#pragma unroll
-      for (int i = 0; i < RM; ++i)
-        a_frag[i] = read_frag<V8>(lds_a(cur), wr + i * 16, ks);
-      {
-        const int c0 = wc, c1 = wc + 16;
-        frag_tr2<V8>(
-            frag_tr_base(lds_b(cur) + (c0 >> 6) * 8192, c0 & 63, ks * 32),
-            frag_tr_base(lds_b(cur) + (c1 >> 6) * 8192, c1 & 63, ks * 32),
-            b_frag);
-      }
-#pragma unroll
-      for (int i = 0; i < RM; ++i) {
-#pragma unroll
-        for (int j = 0; j < RN; ++j) {
-          acc[i][j] = mfma16<V8>(a_frag[i], b_frag[j], acc[i][j]);
-        }
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    cur ^= 1;
-  }
-
-  const int crow_off = (lane >> 4) * 4;
-  const int ccol = lane & 15;
-#pragma unroll
-  for (int i = 0; i < RM; ++i) {
-#pragma unroll
-    for (int j = 0; j < RN; ++j) {
-      const long k = k0 + wc + j * 16 + ccol;
-      if (k >= K) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long m = m0 + wr + i * 16 + crow_off + r;
-        if (m >= M) continue;
-        C[m * K + k] = from_f32<T>(acc[i][j][r]);
-      }
-    }
-  }
-}
-
 struct TileChoice { int bm, bn; };
 
 static TileChoice pick_tile_nn(long M, long K) {
-  if (const char* env = std::getenv("PDNLP_NN_TILE")) {
-    int bm, bn;
-    if (std::sscanf(env, "%dx%d", &bm, &bn) == 2
-        && (bn == 64 || K % bn == 0))  // see OOB note below
-      return {bm, bn};
-  }
-  auto wgs = [&](int bm, int bn) {
-    return ((M + bm - 1) / bm) * ((K + bn - 1) / bn);
-  };
   // BN=128 tiles stage B in two 64-column groups: the LAST tile would read
   // past the K extent unless K % 128 == 0 (B's contraction ROWS are
   // clamped, its columns are not) — a 64-wide tile is always in-bounds
   // because the host requires K % 64 == 0
+  if (const char* env = std::getenv("PDNLP_NN_TILE")) {
+    // the grid is sized from this tile, so only a tile that has a kernel
+    // and stays in bounds may pass
+    int bm = 0, bn = 0;
+    const bool parsed = std::sscanf(env, "%dx%d", &bm, &bn) == 2;
+    TORCH_CHECK(parsed && ((bm == 64 && (bn == 64 || bn == 128)) ||
+                           (bm == 128 && bn == 128)),
+                "PDNLP_NN_TILE=", env,
+                ": accepted tiles are 64x64, 64x128, 128x128");
+    TORCH_CHECK(bn == 64 || K % 128 == 0, "PDNLP_NN_TILE=", env,
+                ": a 128-wide tile needs K % 128 == 0, K is ", K);
+    return {bm, bn};
+  }
+  auto wgs = [&](int bm, int bn) {
+    return ((M + bm - 1) / bm) * ((K + bn - 1) / bn);
+  };
   if (K % 128 != 0) return {64, 64};
   // swept on MI355X (gpurun_out/sweep_dgemm.log): skinny outputs want the
   // chip-filling 64x64 grid; K>768 wants 128x128 intensity once >=384 WGs
@@ -270,14 +159,34 @@ static TileChoice pick_tile_nn(long M, long K) {
     if (wgs(64, 64) >= 512) return {64, 64};
     return {64, 128};
   }
-  // 256x128 (dynamic-LDS raw-barrier variant below) measured NEUTRAL vs
-  // 128x128 on every deep-grid shape (gpurun_out/sweep_256.log: 550/919/787
-  // vs 562/913/795 TF) — 96 KB LDS costs the second block/CU that implicit
-  // wave overlap feeds on; reachable via PDNLP_NN_TILE=256x128 for sweeps
   if (wgs(128, 128) >= 384) return {128, 128};
   return {64, 128};
 }
 
+template <typename T>
+using NnKernel = void (*)(const T*, const T*, T*, long, long, long, int, int,
+                          const T*);
+
+// pick_tile_nn returns only the three tiles listed here. 8 waves are the
+// default; PDNLP_NN_W4 selects 4 for the plain 64-row tiles and has no
+// effect on 128x128 or on the fused-add kernels, which exist at 8 waves
+// only.
+template <typename T, typename V8>
+NnKernel<T> nn_kernel(TileChoice tc, int nw, bool addd) {
+  const bool w8 = nw == 8;
+  if (tc.bm == 64 && tc.bn == 64)
+    return addd ? gemm_nn_kernel<T, V8, 64, 64, 8, true>
+           : w8 ? gemm_nn_kernel<T, V8, 64, 64, 8, false>
+                : gemm_nn_kernel<T, V8, 64, 64, 4, false>;
+  if (tc.bm == 64 && tc.bn == 128)
+    return addd ? gemm_nn_kernel<T, V8, 64, 128, 8, true>
+           : w8 ? gemm_nn_kernel<T, V8, 64, 128, 8, false>
+                : gemm_nn_kernel<T, V8, 64, 128, 4, false>;
+  return addd ? gemm_nn_kernel<T, V8, 128, 128, 8, true>
+              : gemm_nn_kernel<T, V8, 128, 128, 8, false>;
+}
+
+// C = A @ B, plus D when `dptr` is given (the fused residual-grad add)
 template <typename T, typename V8>
 void launch_nn(const torch::Tensor& A, const torch::Tensor& B,
                torch::Tensor& C, hipStream_t stream,
@@ -287,56 +196,14 @@ void launch_nn(const torch::Tensor& A, const torch::Tensor& B,
   const int tiles_m = (int)((M + tc.bm - 1) / tc.bm);
   const int tiles_n = (int)((K + tc.bn - 1) / tc.bn);
   const int nwg = tiles_m * tiles_n;
-  const bool w8 = std::getenv("PDNLP_NN_W4") == nullptr;  // 8 waves default
-  const bool rb = std::getenv("PDNLP_NN_RB") != nullptr;
-  if (dptr != nullptr) {
-    // fused +D epilogue: instantiated for the default tiles only
-#define LAUNCH_NN_D(BMV, BNV, NWV)                                             \
-    hipLaunchKernelGGL((gemm_nn_kernel<T, V8, BMV, BNV, NWV, false, true>),    \
-                       dim3(nwg), dim3(NWV * WAVE), 0, stream,                 \
-                       (const T*)A.data_ptr(), (const T*)B.data_ptr(),         \
-                       (T*)C.data_ptr(), M, N, K, tiles_n, nwg, dptr)
-    if (tc.bm == 64 && tc.bn == 64) LAUNCH_NN_D(64, 64, 8);
-    else if (tc.bm == 64 && tc.bn == 128) LAUNCH_NN_D(64, 128, 8);
-    else LAUNCH_NN_D(128, 128, 8);
-#undef LAUNCH_NN_D
-    return;
-  }
-#define LAUNCH_NN(BMV, BNV, NWV)                                               \
-  do {                                                                         \
-    if (rb)                                                                    \
-      hipLaunchKernelGGL((gemm_nn_kernel<T, V8, BMV, BNV, NWV, true>),         \
-                         dim3(nwg), dim3(NWV * WAVE), 0, stream,               \
-                         (const T*)A.data_ptr(), (const T*)B.data_ptr(),       \
-                         (T*)C.data_ptr(), M, N, K, tiles_n, nwg);             \
-    else                                                                       \
-      hipLaunchKernelGGL((gemm_nn_kernel<T, V8, BMV, BNV, NWV, false>),        \
-                         dim3(nwg), dim3(NWV * WAVE), 0, stream,               \
-                         (const T*)A.data_ptr(), (const T*)B.data_ptr(),       \
-                         (T*)C.data_ptr(), M, N, K, tiles_n, nwg);             \
-  } while (0)
-  if (tc.bm == 64 && tc.bn == 64) {
-    if (w8) LAUNCH_NN(64, 64, 8);
-    else LAUNCH_NN(64, 64, 4);
-  } else if (tc.bm == 64 && tc.bn == 128) {
-    if (w8) LAUNCH_NN(64, 128, 8);
-    else LAUNCH_NN(64, 128, 4);
-  } else if (tc.bm == 256 && tc.bn == 128) {
-    constexpr int shmem = 2 * (256 * 128) + 2 * (2 * 8192);  // 96 KB
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipFuncSetAttribute((const void*)&gemm_nn_256_kernel<T, V8>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_nn_256_kernel<T, V8>), dim3(nwg), dim3(512),
-                       shmem, stream, (const T*)A.data_ptr(),
-                       (const T*)B.data_ptr(), (T*)C.data_ptr(), M, N, K,
-                       tiles_n, nwg);
-  } else {
-    LAUNCH_NN(128, 128, 8);
-  }
-#undef LAUNCH_NN
+  const bool addd = dptr != nullptr;
+  const bool w4 = !addd && tc.bm == 64 &&
+                  std::getenv("PDNLP_NN_W4") != nullptr;
+  const int nw = w4 ? 4 : 8;
+  auto kernel = nn_kernel<T, V8>(tc, nw, addd);
+  hipLaunchKernelGGL(kernel, dim3(nwg), dim3(nw * WAVE), 0, stream,
+                     (const T*)A.data_ptr(), (const T*)B.data_ptr(),
+                     (T*)C.data_ptr(), M, N, K, tiles_n, nwg, dptr);
 }
 
 }  // namespace

@@ -523,6 +523,75 @@ def test_gemm_nn_tiles_agree():
                                        rtol=1e-3, atol=1e-2), (tile, w4)
 
 
+def test_gemm_nt_tiles_agree(monkeypatch):
+    """Every (tile, waves) instantiation of the forward GEMM computes the same
+    C and pre-activation as the auto-picked one. M=200 leaves a row tail,
+    N=192 a column tail for the 128-wide tiles, K=192 is three K-tiles, so
+    both LDS buffers are reused."""
+    e = ext()
+    torch.manual_seed(12)
+    M, N, K = 200, 192, 192
+    A = (torch.randn(M, K, device=DEV) / math.sqrt(K)).bfloat16()
+    W = torch.randn(N, K, device=DEV).bfloat16()
+    bias = torch.randn(N, device=DEV).bfloat16()
+    monkeypatch.delenv("PDNLP_GEMM_TILE", raising=False)
+    monkeypatch.delenv("PDNLP_GEMM_W4", raising=False)
+    C0, pre0 = e.gemm_nt_fwd(A, W, bias, "gelu")
+    pre_ref = A.float() @ W.float().t() + bias.float()
+    assert (pre0.float() - pre_ref).abs().max().item() < 0.05
+    assert (C0.float() - F.gelu(pre_ref)).abs().max().item() < 0.05
+    # 128x64 exists at 4 waves only and takes them without PDNLP_GEMM_W4
+    pairs = [("64x64", 8), ("64x64", 4), ("64x128", 8), ("64x128", 4),
+             ("128x64", 4), ("128x128", 8), ("128x128", 4)]
+    for tile, waves in pairs:
+        monkeypatch.setenv("PDNLP_GEMM_TILE", tile)
+        if waves == 4 and tile != "128x64":
+            monkeypatch.setenv("PDNLP_GEMM_W4", "1")
+        else:
+            monkeypatch.delenv("PDNLP_GEMM_W4", raising=False)
+        C, pre = e.gemm_nt_fwd(A, W, bias, "gelu")
+        for name, got, want in (("C", C, C0), ("pre", pre, pre0)):
+            torch.testing.assert_close(
+                got.float(), want.float(), rtol=1e-3, atol=1e-2,
+                msg=lambda m: f"{tile} w{waves} {name}: {m}")
+
+
+def test_gemm_tile_override_rejected(monkeypatch):
+    """A tile override that has no kernel is refused on the host, before
+    anything is launched; without the override the same call works."""
+    e = ext()
+    torch.manual_seed(13)
+    A = (torch.randn(128, 128, device=DEV) / math.sqrt(128)).bfloat16()
+    B = torch.randn(128, 128, device=DEV, dtype=torch.bfloat16)
+    D = torch.randn(128, 128, device=DEV, dtype=torch.bfloat16)
+    nobias = torch.Tensor().to(DEV)
+    # outputs are ~N(0,1) rounded to bf16 (2^-9 relative): the file's bf16
+    # roundoff tolerance
+    tol = dict(rtol=2e-2, atol=2e-2)
+
+    monkeypatch.setenv("PDNLP_GEMM_TILE", "256x256")
+    with pytest.raises(RuntimeError):
+        e.gemm_nt_fwd(A, B, nobias, "none")
+    monkeypatch.delenv("PDNLP_GEMM_TILE")
+    C, _ = e.gemm_nt_fwd(A, B, nobias, "none")
+    torch.testing.assert_close(C.float(), A.float() @ B.float().t(),
+                               rtol=2e-2, atol=2e-2)
+
+    for tile in ("256x128", "128x64"):
+        monkeypatch.setenv("PDNLP_NN_TILE", tile)
+        with pytest.raises(RuntimeError):
+            e.gemm_nn(A, B)
+    monkeypatch.setenv("PDNLP_NN_TILE", "256x128")
+    with pytest.raises(RuntimeError):
+        e.gemm_nn_add(A, B, D)
+    monkeypatch.delenv("PDNLP_NN_TILE")
+    ref = A.float() @ B.float()
+    torch.testing.assert_close(e.gemm_nn(A, B).float(), ref,
+                               rtol=2e-2, atol=2e-2)
+    torch.testing.assert_close(e.gemm_nn_add(A, B, D).float(),
+                               ref + D.float(), rtol=2e-2, atol=2e-2)
+
+
 def test_gemm_tn_w4_w8_agree():
     import os
     e = ext()

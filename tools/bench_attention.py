@@ -1,4 +1,4 @@
-import os, sys, time, torch
+import sys, time, torch
 sys.path.insert(0, ".")
 from pdnlp_amd.ops import ext
 e = ext()
@@ -21,4 +21,4 @@ for (B, nh, S) in [(16, 16, 512), (32, 12, 128)]:
         for _ in range(30): fn()
         torch.cuda.synchronize()
         us = (time.perf_counter()-t0)/30*1e6
-        print(f"B{B} nh{nh} S{S} {name}: {us:.0f} us  rb={os.environ.get('PDNLP_FA_RB','0')}")
+        print(f"B{B} nh{nh} S{S} {name}: {us:.0f} us")
