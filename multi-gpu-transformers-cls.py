@@ -12,6 +12,7 @@ import os
 
 import numpy as np
 
+from pdnlp_amd.cli import _unpad_kw
 from pdnlp_amd.config import Args
 from pdnlp_amd.data import (ClsDataset, Collate, SyntheticClsDataset,
                             build_tokenizer, load_data, train_dev_split)
@@ -42,15 +43,18 @@ def main():
         data = load_data(base.data_path, limit=base.data_limit)
         train_data, dev_data = train_dev_split(data, base.ratio, base.seed)
         tok = build_tokenizer(base.model_path)
-        collate = Collate(tok, base.max_seq_len, label_key="labels")
+        collate = Collate(tok, base.max_seq_len, label_key="labels",
+                          **_unpad_kw(base))
         train_ds, dev_ds = ClsDataset(train_data), ClsDataset(dev_data)
     else:
         n_train = int(base.data_limit * base.ratio)
         train_ds = SyntheticClsDataset(n_train, base.max_seq_len, seed=base.seed)
         dev_ds = SyntheticClsDataset(base.data_limit - n_train,
                                      base.max_seq_len, seed=base.seed + 1)
-        collate = Collate(None, base.max_seq_len, label_key="labels")
+        collate = Collate(None, base.max_seq_len, label_key="labels",
+                          **_unpad_kw(base))
     model = build_model(base.model, model_path=base.model_path)
+    hf_args.unpad = base.unpad
     trainer = HFStyleTrainer(model, hf_args, train_dataset=train_ds,
                              eval_dataset=dev_ds, data_collator=collate,
                              compute_metrics=compute_metrics)

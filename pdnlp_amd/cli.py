@@ -31,13 +31,20 @@ from .utils.logging import rank0_print
 _VOCAB = {"tiny": 512, "roberta-base": 50265}
 
 
+def _unpad_kw(args: Args) -> dict:
+    """Collate options of the padding-free path (``--unpad true``)."""
+    roberta = getattr(args, "model", "bert-base") == "roberta-base"
+    return dict(unpad=getattr(args, "unpad", False),
+                pad_token_id=1 if roberta else 0, roberta=roberta)
+
+
 def build_dataloaders(args: Args, world_size: int, rank: int):
     vocab_size = _VOCAB.get(getattr(args, "model", "bert-base"), 21128)
     if os.path.isfile(args.data_path):
         data = load_data(args.data_path, limit=args.data_limit)
         train_data, dev_data = train_dev_split(data, args.ratio, args.seed)
         tok = build_tokenizer(args.model_path, vocab_size)
-        collate = Collate(tok, args.max_seq_len)
+        collate = Collate(tok, args.max_seq_len, **_unpad_kw(args))
         train_ds, dev_ds = ClsDataset(train_data), ClsDataset(dev_data)
     else:
         from dataclasses import fields
@@ -59,7 +66,7 @@ def build_dataloaders(args: Args, world_size: int, rank: int):
                                        seed=args.seed)
         dev_ds = SyntheticClsDataset(n - n_train, args.max_seq_len, vocab_size,
                                      seed=args.seed + 1)
-        collate = Collate(None, args.max_seq_len)
+        collate = Collate(None, args.max_seq_len, **_unpad_kw(args))
 
     train_sampler = None
     if world_size > 1:

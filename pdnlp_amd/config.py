@@ -107,6 +107,9 @@ class Args:
     ratio: float = 0.92                # train/dev split
     data_limit: int = 10000            # reference slices first 10k samples
     num_workers: int = 2
+    unpad: bool = False                # padding-free batches: pack the real
+                                       # tokens into one [T] stream (collate)
+                                       # + variable-length attention
 
     # optimization
     train_batch_size: int = 32         # per GPU

@@ -13,14 +13,70 @@ from __future__ import annotations
 import torch
 
 
+def pack_batch(batch, multiple: int = 64, label_key: str = "label",
+               pad_token_id: int = 0, roberta: bool = False):
+    """Padded batch dict ([B, S] ids/mask/types + labels) -> packed token
+    stream for the padding-free path (``--unpad``).
+
+    Real tokens (``attention_mask == 1``, which must be a prefix of ones in
+    every row) are concatenated row after row; the stream is padded to a
+    multiple of ``multiple`` rows (the GEMM row granule) with
+    ``pad_token_id`` / type 0 / position 0. ``cu_seqlens`` [B+1] int32 holds
+    the sequence boundaries, ``max_seqlen`` the longest sequence (a host int,
+    so the attention launch needs no device sync). Position ids restart per
+    sequence; RoBERTa's are ``pad_token_id + 1 + i`` as on the padded path.
+    """
+    mask = batch["attention_mask"]
+    B, S = mask.shape
+    lens = mask.sum(-1)
+    prefix = (torch.arange(S)[None, :] < lens[:, None]).to(mask.dtype)
+    if not torch.equal(mask, prefix):
+        raise ValueError("pack_batch: every attention_mask row must be a "
+                         "prefix of ones followed by zeros")
+    if int(lens.min()) < 1:
+        raise ValueError("pack_batch: every sequence needs >= 1 real token")
+    cu = torch.zeros(B + 1, dtype=torch.int32)
+    cu[1:] = lens.cumsum(0)
+    total = int(cu[-1])
+    T = (total + multiple - 1) // multiple * multiple
+    keep = mask.bool()
+    pos = torch.arange(S)[None, :].expand(B, S)[keep]
+    if roberta:
+        pos = pos + pad_token_id + 1
+    input_ids = torch.full((T,), pad_token_id, dtype=torch.long)
+    token_type_ids = torch.zeros(T, dtype=torch.long)
+    position_ids = torch.zeros(T, dtype=torch.long)
+    input_ids[:total] = batch["input_ids"][keep]
+    token_type_ids[:total] = batch["token_type_ids"][keep]
+    position_ids[:total] = pos
+    return {
+        "input_ids": input_ids,
+        "token_type_ids": token_type_ids,
+        "position_ids": position_ids,
+        "cu_seqlens": cu,
+        "max_seqlen": int(lens.max()),
+        label_key: batch[label_key],
+    }
+
+
 class Collate:
-    def __init__(self, tokenizer, max_seq_len: int = 128, label_key: str = "label"):
+    def __init__(self, tokenizer, max_seq_len: int = 128,
+                 label_key: str = "label", unpad: bool = False,
+                 pad_token_id: int = 0, roberta: bool = False):
         self.tokenizer = tokenizer
         self.max_seq_len = max_seq_len
         self.label_key = label_key  # HF-Trainer mode uses "labels"
+        self.unpad = unpad          # emit the packed stream (pack_batch)
+        self.pad_token_id = pad_token_id
+        self.roberta = roberta
 
     def __call__(self, batch):
-        return self.collate_fn(batch)
+        out = self.collate_fn(batch)
+        if self.unpad:
+            out = pack_batch(out, label_key=self.label_key,
+                             pad_token_id=self.pad_token_id,
+                             roberta=self.roberta)
+        return out
 
     def collate_fn(self, batch):
         if isinstance(batch[0], dict):  # pre-tokenized

@@ -45,6 +45,7 @@ class TrainingArguments:
     seed: int = 123
     gradient_accumulation_steps: int = 1
     dataloader_num_workers: int = 2
+    unpad: bool = False   # the data_collator packs (Collate(unpad=True))
 
 
 class HFStyleTrainer:
@@ -72,6 +73,7 @@ class HFStyleTrainer:
         eargs.log_every = args.logging_steps
         eargs.grad_accum_steps = args.gradient_accumulation_steps
         eargs.seed = args.seed
+        eargs.unpad = args.unpad
         eargs.output_dir = args.output_dir
         eargs.ckpt_path = os.path.join(args.output_dir, "best_model.pt")
         eargs.local_rank = init_distributed()

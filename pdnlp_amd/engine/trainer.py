@@ -62,9 +62,19 @@ class Trainer:
     def on_step(self, batch):
         """H2D copy + forward (reference: multi-gpu-distributed-cls.py:126-137)."""
         input_ids = batch["input_ids"].to(self.device, non_blocking=True)
-        attention_mask = batch["attention_mask"].to(self.device, non_blocking=True)
         token_type_ids = batch["token_type_ids"].to(self.device, non_blocking=True)
         labels = batch[self.label_key].to(self.device, non_blocking=True)
+        if "cu_seqlens" in batch:  # packed stream from Collate(unpad=True)
+            out = self.model(
+                input_ids=input_ids, token_type_ids=token_type_ids,
+                labels=labels,
+                cu_seqlens=batch["cu_seqlens"].to(self.device,
+                                                  non_blocking=True),
+                max_seqlen=int(batch["max_seqlen"]),
+                position_ids=batch["position_ids"].to(self.device,
+                                                      non_blocking=True))
+            return out.loss, out.logits, labels
+        attention_mask = batch["attention_mask"].to(self.device, non_blocking=True)
         out = self.model(input_ids=input_ids, attention_mask=attention_mask,
                          token_type_ids=token_type_ids, labels=labels)
         return out.loss, out.logits, labels
@@ -159,6 +169,14 @@ class Trainer:
         stays eager; dropout reseeds per replay via the device seed."""
         if self._graph is not None:
             return True
+        if getattr(self.args, "hip_graph", False) \
+                and getattr(self.args, "unpad", False):
+            # the packed token count changes every step: nothing to replay
+            if not getattr(self, "_unpad_graph_noted", False):
+                self._unpad_graph_noted = True
+                rank0_print("[pdnlp] --unpad: token shapes vary per step, "
+                            "hipGraph capture disabled (eager steps)")
+            return False
         if not (getattr(self.args, "hip_graph", False)
                 and torch.cuda.is_available() and self.world == 1
                 and getattr(self.args, "grad_accum_steps", 1) <= 1
@@ -473,6 +491,11 @@ def build_training(args, model=None, label_key: str = "label"):
     # rank -> device modulo the visible count: ranks beyond the device
     # count share GPUs (oversubscribed world-2 runs on a 1-GPU box) instead
     # of crashing with "invalid device ordinal"
+    if getattr(args, "unpad", False) and args.strategy == "dp":
+        raise ValueError(
+            "--unpad true cannot be combined with strategy=dp: single-process "
+            "DataParallel splits the batch on dim 0, which a packed token "
+            "stream does not have. Use strategy=ddp (one process per GPU).")
     ndev = max(torch.cuda.device_count(), 1)
     device = torch.device(f"cuda:{args.local_rank % ndev}"
                           if torch.cuda.is_available() else "cpu")

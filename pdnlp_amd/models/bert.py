@@ -56,13 +56,17 @@ class BertEmbeddings(nn.Module):
             torch.arange(cfg.max_position_embeddings).unsqueeze(0),
             persistent=False)
 
-    def forward(self, input_ids, token_type_ids, training: bool):
-        B, S = input_ids.shape
-        if self.cfg.model_type == "roberta":
+    def forward(self, input_ids, token_type_ids, training: bool,
+                position_ids=None):
+        # a packed stream brings its own per-sequence position_ids
+        if position_ids is not None:
+            pass
+        elif self.cfg.model_type == "roberta":
             # HF roberta: position ids from non-pad positions, offset by pad id
             mask = (input_ids != self.cfg.pad_token_id).long()
             position_ids = mask.cumsum(-1) * mask + self.cfg.pad_token_id
         else:
+            B, S = input_ids.shape
             position_ids = self.position_ids[:, :S].expand(B, S)
         if token_type_ids is None:
             token_type_ids = torch.zeros_like(input_ids)
@@ -153,10 +157,10 @@ class BertLayer(nn.Module):
         self.output = BertOutput(cfg)
 
     def forward(self, h: torch.Tensor, attn_mask: Optional[torch.Tensor],
-                training: bool) -> torch.Tensor:
+                training: bool, cu_seqlens: Optional[torch.Tensor] = None,
+                max_seqlen: Optional[int] = None) -> torch.Tensor:
         cfg = self.cfg
-        B, S, H = h.shape
-        nh, hd = cfg.num_attention_heads, cfg.head_dim
+        nh = cfg.num_attention_heads
         a = self.attention.self
         # fused QKV projection: one [H, 3H] GEMM (K2), then fused flash
         # attention straight on the packed projection (K3-K5 + K16).
@@ -164,8 +168,15 @@ class BertLayer(nn.Module):
         # node so the residual-grad fan-in add fuses into the dX GEMM
         # epilogue (ops/functional.py _LinearForkHipFn)
         qkv, h_res = ops.linear_fork(h, a.qkv_weight, a.qkv_bias)
-        ctx = ops.attention_packed(qkv, attn_mask, nh,
-                                   cfg.attention_probs_dropout_prob, training)
+        if cu_seqlens is not None:
+            # packed stream h [1, T, H]: sequence-boundary-aware attention
+            ctx = ops.attention_varlen(
+                qkv[0], cu_seqlens, max_seqlen, nh,
+                cfg.attention_probs_dropout_prob, training).unsqueeze(0)
+        else:
+            ctx = ops.attention_packed(
+                qkv, attn_mask, nh, cfg.attention_probs_dropout_prob,
+                training)
         # attention output projection + fused bias/dropout/residual/LN (K6);
         # the bias gradient comes out of the projection's dW GEMM
         ao = self.attention.output
@@ -207,23 +218,46 @@ class BertModel(nn.Module):
         self._grad_ckpt = False
         self._ckpt_cpu_offload = False
 
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None):
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None,
+                cu_seqlens=None, max_seqlen=None, position_ids=None):
+        """Padded: ``input_ids`` [B, S] + ``attention_mask``. Packed
+        (``cu_seqlens`` given): ``input_ids``/``token_type_ids``/
+        ``position_ids`` are the 1-D token stream [T] of ``pack_batch``,
+        ``attention_mask`` is ignored, and the hidden states come back as
+        the packed [1, T, H] stream."""
         training = self.training
-        if attention_mask is None:
-            attention_mask = torch.ones_like(input_ids)
-        # additive mask in compute dtype: 0 keep / -10000 drop (HF convention)
-        dtype = self.embeddings.word_embeddings.weight.dtype
-        addmask = (1.0 - attention_mask[:, None, None, :].to(dtype)) * -10000.0
-        h = self.embeddings(input_ids, token_type_ids, training)
+        if cu_seqlens is not None:
+            assert input_ids.dim() == 1 and position_ids is not None \
+                and max_seqlen is not None, \
+                "packed input needs 1-D input_ids, position_ids, max_seqlen"
+            tt = token_type_ids.unsqueeze(0) \
+                if token_type_ids is not None else None
+            h = self.embeddings(input_ids.unsqueeze(0), tt, training,
+                                position_ids.unsqueeze(0))
+            addmask = None
+        else:
+            if attention_mask is None:
+                attention_mask = torch.ones_like(input_ids)
+            # additive mask in compute dtype: 0 keep / -10000 drop (HF
+            # convention)
+            dtype = self.embeddings.word_embeddings.weight.dtype
+            addmask = (1.0 - attention_mask[:, None, None, :].to(dtype)) \
+                * -10000.0
+            h = self.embeddings(input_ids, token_type_ids, training)
         for layer in self.encoder.layer:
             if self._grad_ckpt and training:
                 h = _checkpoint_layer(layer, h, addmask, training,
-                                      self._ckpt_cpu_offload)
+                                      self._ckpt_cpu_offload, cu_seqlens,
+                                      max_seqlen)
             else:
-                h = layer(h, addmask, training)
+                h = layer(h, addmask, training, cu_seqlens, max_seqlen)
+        if cu_seqlens is not None:
+            cls = _packed_cls(h, cu_seqlens)
+        else:
+            cls = h[:, 0]
         pooled = None
         if self.pooler is not None:
-            pooled = ops.linear(h[:, 0], self.pooler.dense.weight,
+            pooled = ops.linear(cls, self.pooler.dense.weight,
                                 self.pooler.dense.bias, act="tanh")
         return h, pooled
 
@@ -235,7 +269,13 @@ class BertModel(nn.Module):
         self._grad_ckpt = False
 
 
-def _checkpoint_layer(layer, h, mask, training, cpu_offload):
+def _packed_cls(h, cu_seqlens):
+    """[B, H] first-token rows of a packed hidden stream h [1, T, H]."""
+    return h[0].index_select(0, cu_seqlens[:-1].long())
+
+
+def _checkpoint_layer(layer, h, mask, training, cpu_offload,
+                      cu_seqlens=None, max_seqlen=None):
     """Activation checkpointing (deepspeed-capability equivalent,
     reference config: multi-gpu-deepspeed-cls.py:240-244), optional CPU
     offload of the saved input over PCIe."""
@@ -243,8 +283,10 @@ def _checkpoint_layer(layer, h, mask, training, cpu_offload):
     if cpu_offload:
         ctx = torch.autograd.graph.save_on_cpu(pin_memory=True)
         with ctx:
-            return cp.checkpoint(layer, h, mask, training, use_reentrant=False)
-    return cp.checkpoint(layer, h, mask, training, use_reentrant=False)
+            return cp.checkpoint(layer, h, mask, training, cu_seqlens,
+                                 max_seqlen, use_reentrant=False)
+    return cp.checkpoint(layer, h, mask, training, cu_seqlens, max_seqlen,
+                         use_reentrant=False)
 
 
 class BertForSequenceClassification(nn.Module):
@@ -257,8 +299,10 @@ class BertForSequenceClassification(nn.Module):
         self.apply(_init_weights(cfg))
 
     def forward(self, input_ids, attention_mask=None, token_type_ids=None,
-                labels=None):
-        _, pooled = self.bert(input_ids, attention_mask, token_type_ids)
+                labels=None, cu_seqlens=None, max_seqlen=None,
+                position_ids=None):
+        _, pooled = self.bert(input_ids, attention_mask, token_type_ids,
+                              cu_seqlens, max_seqlen, position_ids)
         pooled = ops.dropout(pooled, self.cfg.hidden_dropout_prob, self.training)
         logits = ops.linear(pooled, self.classifier.weight, self.classifier.bias)
         loss = ops.cross_entropy(logits, labels) if labels is not None else None
@@ -293,9 +337,13 @@ class RobertaForSequenceClassification(nn.Module):
         self.apply(_init_weights(cfg))
 
     def forward(self, input_ids, attention_mask=None, token_type_ids=None,
-                labels=None):
-        h, _ = self.roberta(input_ids, attention_mask, token_type_ids)
-        x = ops.dropout(h[:, 0], self.cfg.hidden_dropout_prob, self.training)
+                labels=None, cu_seqlens=None, max_seqlen=None,
+                position_ids=None):
+        h, _ = self.roberta(input_ids, attention_mask, token_type_ids,
+                            cu_seqlens, max_seqlen, position_ids)
+        cls = _packed_cls(h, cu_seqlens) if cu_seqlens is not None \
+            else h[:, 0]
+        x = ops.dropout(cls, self.cfg.hidden_dropout_prob, self.training)
         x = ops.linear(x, self.classifier.dense.weight,
                        self.classifier.dense.bias, act="tanh")
         x = ops.dropout(x, self.cfg.hidden_dropout_prob, self.training)

@@ -79,6 +79,7 @@ from .functional import (  # noqa: F401,E402
     bias_gelu,
     attention,
     attention_packed,
+    attention_varlen,
     masked_softmax,
     cross_entropy,
     bias_dropout_residual_layernorm,

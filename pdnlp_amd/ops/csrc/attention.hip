@@ -22,6 +22,14 @@
 //    native MFMA A@B^T form. Transposed B-operands (V^T, K^T, Q^T, dO^T)
 //    come from ds_read_b64_tr_b16 hardware transpose reads.
 //
+// VARLEN instantiations run the same three kernels over a padding-free
+// token stream [T, 3H]: sequence b is rows cu_seqlens[b]..cu_seqlens[b+1],
+// the grid is (ceil(max_seqlen/64), B*nh), a block reads its sequence bounds
+// once in the prologue (never inside the KV loop) and leaves at once when
+// its 64-row tile lies past the sequence end. Tail keys are masked and tail
+// rows are never stored, so the zero-filled outputs stay exactly zero
+// outside the sequences.
+//
 // LDS image convention: every tile is a gfx950 "tr-image" (see tr_addr
 // below) that serves both normal and hardware-transposed fragment reads
 // from the same staging.
@@ -148,26 +156,51 @@ __device__ __forceinline__ float qsum(float x) {
   return x;
 }
 
+// dropout counter for probability (qrow, key): qrow is the head-major row
+// (padded: bh*S + row; VARLEN: h*T + packed row), key the key index inside
+// the sequence. Identical in forward, dQ and dK/dV. VARLEN strides rows by
+// the 1024 key cap instead of S, so nh*T <= 2^22 (host-checked) cannot wrap.
+template <bool VARLEN>
+__device__ __forceinline__ unsigned int drop_idx(unsigned int qrow,
+                                                 unsigned int key, int S) {
+  return VARLEN ? (qrow << 10) + key : qrow * S + key;
+}
+
+// VARLEN sequence length of batch entry b, clamped so that a bad cu_seqlens
+// can neither leave the [T] stream nor the 1024-entry LDS rows
+__device__ __forceinline__ int varlen_len(const int* cu_seqlens, long b,
+                                          long row0, int T) {
+  const long len = cu_seqlens[b + 1] - row0;
+  const long cap = T - row0 < 1024 ? T - row0 : 1024;
+  return (int)(len < cap ? len : cap);
+}
+
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
 
-template <typename T, typename V8, bool HAS_MASK, bool DROP, bool PRELOAD>
+template <typename T, typename V8, bool HAS_MASK, bool DROP, bool PRELOAD,
+          bool VARLEN>
 __global__ __launch_bounds__(NTHREADS)
 void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
                    T* __restrict__ o, float* __restrict__ lse,
                    const unsigned long long* __restrict__ seed_base,
                    unsigned long long salt, float scale, float p,
-                   int nh, int S) {
+                   int nh, int S, const int* __restrict__ cu_seqlens) {
   scale *= 1.4426950408889634f;  // exp2 domain (log2 e)
   const int bh = blockIdx.y;
   const long b = bh / nh, h = bh % nh;
   const long rb = blockIdx.x;
   const long H = (long)nh * 64, ld = 3 * H;
-  const T* qbase = qkv + b * S * ld + h * 64;
+  // the block's sequence is rows [row0, row0 + len); VARLEN: S carries T
+  const long row0 = VARLEN ? (long)cu_seqlens[b] : b * S;
+  const int len = VARLEN ? varlen_len(cu_seqlens, b, row0, S) : S;
+  if (VARLEN && rb * 64 >= len) return;  // block-uniform, before any barrier
+  const long stat0 = VARLEN ? h * S + row0 : (long)bh * S;  // lse row base
+  const T* qbase = qkv + row0 * ld + h * 64;
   const T* kbase = qbase + H;
   const T* vbase = qbase + 2 * H;
-  T* obase = o + b * S * H + h * 64;
+  T* obase = o + row0 * H + h * 64;
 
   __shared__ __attribute__((aligned(16))) char q_lds[64 * 128];
   __shared__ __attribute__((aligned(16))) char k_lds[2][64 * 128];
@@ -185,14 +218,14 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
   const unsigned int seed32 = (unsigned int)(seed ^ (seed >> 32));
   const float inv_keep = DROP ? 1.f / (1.f - p) : 1.f;
 
-  stage64<T>(qbase, ld, rb * 64, S, q_lds);
-  stage64<T>(kbase, ld, 0, S, k_lds[0]);
-  stage64<T>(vbase, ld, 0, S, v_lds[0]);
-  if (PRELOAD && S > 64) {
+  stage64<T>(qbase, ld, rb * 64, len, q_lds);
+  stage64<T>(kbase, ld, 0, len, k_lds[0]);
+  stage64<T>(vbase, ld, 0, len, v_lds[0]);
+  if (PRELOAD && len > 64) {
     // S <= 128: the whole K/V fits the double buffers — stage everything
     // up front and run the KV loop with NO mid-loop barriers/waits
-    stage64<T>(kbase, ld, 64, S, k_lds[1]);
-    stage64<T>(vbase, ld, 64, S, v_lds[1]);
+    stage64<T>(kbase, ld, 64, len, k_lds[1]);
+    stage64<T>(vbase, ld, 64, len, v_lds[1]);
   }
   if (HAS_MASK)
     for (int i = threadIdx.x; i < S; i += NTHREADS)
@@ -205,12 +238,12 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
 #pragma unroll
   for (int r = 0; r < 4; ++r) { m[r] = -INFINITY; l[r] = 0.f; }
 
-  const int nt = S / 64;
+  const int nt = VARLEN ? (len + 63) / 64 : S / 64;
   int cur = 0;
   for (int t = 0; t < nt; ++t) {
     if (!PRELOAD && t + 1 < nt) {
-      stage64<T>(kbase, ld, (long)(t + 1) * 64, S, k_lds[cur ^ 1]);
-      stage64<T>(vbase, ld, (long)(t + 1) * 64, S, v_lds[cur ^ 1]);
+      stage64<T>(kbase, ld, (long)(t + 1) * 64, len, k_lds[cur ^ 1]);
+      stage64<T>(vbase, ld, (long)(t + 1) * 64, len, v_lds[cur ^ 1]);
     }
     f32x4 acc_s[4] = {};
 #pragma unroll
@@ -235,6 +268,11 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         s[j][r] = acc_s[j][r] * scale + mv[j];
+        // keys past the sequence end (the staged rows there are clamped
+        // copies): score -inf, so P is exactly 0. Tile t always holds at
+        // least one real key, which keeps the running max finite.
+        if (VARLEN && t * 64 + j * 16 + (lane & 15) >= len)
+          s[j][r] = -INFINITY;
         x = fmaxf(x, s[j][r]);
       }
       const float mn = fmaxf(m[r], qmax(x));
@@ -254,13 +292,16 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int prow = wr + (lane >> 4) * 4 + r;
-      const unsigned int grow = (unsigned int)bh * S + rb * 64 + prow;
+      const unsigned int grow =
+          VARLEN ? (unsigned int)(stat0 + rb * 64 + prow)
+                 : (unsigned int)bh * S + rb * 64 + prow;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int kcol = j * 16 + (lane & 15);
         float pv = s[j][r];
         if (DROP) {
-          const unsigned int rr = hash_rng32(seed32, grow * S + t * 64 + kcol);
+          const unsigned int rr = hash_rng32(
+              seed32, drop_idx<VARLEN>(grow, t * 64 + kcol, S));
           pv = (rr * 2.3283064365386963e-10f) >= p ? pv * inv_keep : 0.f;
         }
         *reinterpret_cast<unsigned short*>(
@@ -294,11 +335,12 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
     const int prow = wr + (lane >> 4) * 4 + r;
     const long grow = rb * 64 + prow;
     const float invl = l[r] > 0.f ? 1.f / l[r] : 0.f;
+    if (VARLEN && grow >= len) continue;  // tail rows are never stored
 #pragma unroll
     for (int jd = 0; jd < 4; ++jd)
       obase[grow * H + jd * 16 + ccol] = from_f32<T>(acc_o[jd][r] * invl);
     if (ccol == 0)
-      lse[(long)bh * S + grow] = m[r] + log2f(fmaxf(l[r], 1e-30f));
+      lse[stat0 + grow] = m[r] + log2f(fmaxf(l[r], 1e-30f));
   }
 }
 
@@ -306,7 +348,8 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
 // backward dQ: grid over 64-row blocks; recompute P from lse, stream K/V
 // ---------------------------------------------------------------------------
 
-template <typename T, typename V8, bool HAS_MASK, bool DROP, bool PRELOAD>
+template <typename T, typename V8, bool HAS_MASK, bool DROP, bool PRELOAD,
+          bool VARLEN>
 __global__ __launch_bounds__(NTHREADS)
 void fa_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
                       const T* __restrict__ o, const float* __restrict__ lse,
@@ -314,18 +357,23 @@ void fa_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
                       const T* __restrict__ mask, T* __restrict__ dqkv,
                       const unsigned long long* __restrict__ seed_base,
                       unsigned long long salt, float scale, float p,
-                      int nh, int S) {
+                      int nh, int S, const int* __restrict__ cu_seqlens) {
   const float scale2 = scale * 1.4426950408889634f;  // exp2 domain
   const int bh = blockIdx.y;
   const long b = bh / nh, h = bh % nh;
   const long rb = blockIdx.x;
   const long H = (long)nh * 64, ld = 3 * H;
-  const T* qbase = qkv + b * S * ld + h * 64;
+  // sequence rows [row0, row0 + len), as in fa_fwd_kernel
+  const long row0 = VARLEN ? (long)cu_seqlens[b] : b * S;
+  const int len = VARLEN ? varlen_len(cu_seqlens, b, row0, S) : S;
+  if (VARLEN && rb * 64 >= len) return;  // block-uniform, before any barrier
+  const long stat0 = VARLEN ? h * S + row0 : (long)bh * S;  // lse/dvec base
+  const T* qbase = qkv + row0 * ld + h * 64;
   const T* kbase = qbase + H;
   const T* vbase = qbase + 2 * H;
-  const T* dobase = dout + b * S * H + h * 64;
-  const T* obase = o + b * S * H + h * 64;
-  T* dqbase = dqkv + b * S * ld + h * 64;
+  const T* dobase = dout + row0 * H + h * 64;
+  const T* obase = o + row0 * H + h * 64;
+  T* dqbase = dqkv + row0 * ld + h * 64;
 
   __shared__ __attribute__((aligned(16))) char q_lds[64 * 128];
   __shared__ __attribute__((aligned(16))) char do_lds[64 * 128];
@@ -342,16 +390,16 @@ void fa_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
   const unsigned int seed32 = (unsigned int)(seed ^ (seed >> 32));
   const float inv_keep = DROP ? 1.f / (1.f - p) : 1.f;
 
-  stage64<T>(qbase, ld, rb * 64, S, q_lds);
-  stage64<T>(dobase, H, rb * 64, S, do_lds);
+  stage64<T>(qbase, ld, rb * 64, len, q_lds);
+  stage64<T>(dobase, H, rb * 64, len, do_lds);
   // the dS buffer is free until the KV loop: stage O through it to compute
   // Dvec = rowsum(dO * O) here (replaces the separate fa_bwd_pre kernel)
-  stage64<T>(obase, H, rb * 64, S, ds_lds);
-  stage64<T>(kbase, ld, 0, S, k_lds[0]);
-  stage64<T>(vbase, ld, 0, S, v_lds[0]);
-  if (PRELOAD && S > 64) {
-    stage64<T>(kbase, ld, 64, S, k_lds[1]);
-    stage64<T>(vbase, ld, 64, S, v_lds[1]);
+  stage64<T>(obase, H, rb * 64, len, ds_lds);
+  stage64<T>(kbase, ld, 0, len, k_lds[0]);
+  stage64<T>(vbase, ld, 0, len, v_lds[0]);
+  if (PRELOAD && len > 64) {
+    stage64<T>(kbase, ld, 64, len, k_lds[1]);
+    stage64<T>(vbase, ld, 64, len, v_lds[1]);
   }
   if (HAS_MASK)
     for (int i = threadIdx.x; i < S; i += NTHREADS)
@@ -390,20 +438,21 @@ void fa_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
   for (int r = 0; r < 4; ++r) {
     const int prow = wr + (lane >> 4) * 4 + r;
     const long grow = rb * 64 + prow;
-    lse_r[r] = lse[(long)bh * S + grow];
+    // tail rows have no lse (forward never stored one): not read
+    lse_r[r] = (!VARLEN || grow < len) ? lse[stat0 + grow] : 0.f;
     dvec_r[r] = dv_s[prow >> 4][prow & 15];
   }
   // one lane per row publishes Dvec for the dK/dV pass (same stream)
-  if ((lane >> 4) == 0)
-    dvec[(long)bh * S + rb * 64 + wr + (lane & 15)] = dv_s[wid][lane & 15];
+  if ((lane >> 4) == 0 && (!VARLEN || rb * 64 + wr + (lane & 15) < len))
+    dvec[stat0 + rb * 64 + wr + (lane & 15)] = dv_s[wid][lane & 15];
 
   f32x4 acc_dq[4] = {};
-  const int nt = S / 64;
+  const int nt = VARLEN ? (len + 63) / 64 : S / 64;
   int cur = 0;
   for (int t = 0; t < nt; ++t) {
     if (!PRELOAD && t + 1 < nt) {
-      stage64<T>(kbase, ld, (long)(t + 1) * 64, S, k_lds[cur ^ 1]);
-      stage64<T>(vbase, ld, (long)(t + 1) * 64, S, v_lds[cur ^ 1]);
+      stage64<T>(kbase, ld, (long)(t + 1) * 64, len, k_lds[cur ^ 1]);
+      stage64<T>(vbase, ld, (long)(t + 1) * 64, len, v_lds[cur ^ 1]);
     }
     f32x4 acc_s[4] = {}, acc_dp[4] = {};
 #pragma unroll
@@ -428,17 +477,24 @@ void fa_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int prow = wr + (lane >> 4) * 4 + r;
-      const unsigned int grow = (unsigned int)bh * S + rb * 64 + prow;
+      const unsigned int grow =
+          VARLEN ? (unsigned int)(stat0 + rb * 64 + prow)
+                 : (unsigned int)bh * S + rb * 64 + prow;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int kcol = j * 16 + (lane & 15);
         const float pv = exp2f(acc_s[j][r] * scale2 + mv[j] - lse_r[r]);
         float dp = acc_dp[j][r];
         if (DROP) {
-          const unsigned int rr = hash_rng32(seed32, grow * S + t * 64 + kcol);
+          const unsigned int rr = hash_rng32(
+              seed32, drop_idx<VARLEN>(grow, t * 64 + kcol, S));
           dp = (rr * 2.3283064365386963e-10f) >= p ? dp * inv_keep : 0.f;
         }
-        const float dsv = pv * (dp - dvec_r[r]) * scale;
+        float dsv = pv * (dp - dvec_r[r]) * scale;
+        // tail keys and tail query rows: dS is 0 by index (pv there comes
+        // from clamped copies, not from data)
+        if (VARLEN && (t * 64 + kcol >= len || rb * 64 + prow >= len))
+          dsv = 0.f;
         *reinterpret_cast<unsigned short*>(
             ds_lds + tr_addr(prow, kcol)) =
             f32_bits16<T>(dsv);
@@ -468,6 +524,7 @@ void fa_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const long grow = rb * 64 + wr + (lane >> 4) * 4 + r;
+    if (VARLEN && grow >= len) continue;  // tail rows are never stored
 #pragma unroll
     for (int jd = 0; jd < 4; ++jd)
       dqbase[grow * ld + jd * 16 + ccol] = from_f32<T>(acc_dq[jd][r]);
@@ -478,7 +535,8 @@ void fa_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
 // backward dK/dV: grid over 64-key blocks; S^T = K@Q^T so all GEMMs are A@B^T
 // ---------------------------------------------------------------------------
 
-template <typename T, typename V8, bool HAS_MASK, bool DROP, bool PRELOAD>
+template <typename T, typename V8, bool HAS_MASK, bool DROP, bool PRELOAD,
+          bool VARLEN>
 __global__ __launch_bounds__(NTHREADS)
 void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
                        const T* __restrict__ /*o: consumed by the dQ pass*/,
@@ -487,18 +545,23 @@ void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
                        const T* __restrict__ mask, T* __restrict__ dqkv,
                        const unsigned long long* __restrict__ seed_base,
                        unsigned long long salt, float scale, float p,
-                       int nh, int S) {
+                       int nh, int S, const int* __restrict__ cu_seqlens) {
   const float scale2 = scale * 1.4426950408889634f;  // exp2 domain
   const int bh = blockIdx.y;
   const long b = bh / nh, h = bh % nh;
   const long kb = blockIdx.x;
   const long H = (long)nh * 64, ld = 3 * H;
-  const T* qbase = qkv + b * S * ld + h * 64;
+  // sequence rows [row0, row0 + len), as in fa_fwd_kernel
+  const long row0 = VARLEN ? (long)cu_seqlens[b] : b * S;
+  const int len = VARLEN ? varlen_len(cu_seqlens, b, row0, S) : S;
+  if (VARLEN && kb * 64 >= len) return;  // block-uniform, before any barrier
+  const long stat0 = VARLEN ? h * S + row0 : (long)bh * S;  // lse/dvec base
+  const T* qbase = qkv + row0 * ld + h * 64;
   const T* kbase = qbase + H;
   const T* vbase = qbase + 2 * H;
-  const T* dobase = dout + b * S * H + h * 64;
-  T* dkbase = dqkv + b * S * ld + H + h * 64;
-  T* dvbase = dqkv + b * S * ld + 2 * H + h * 64;
+  const T* dobase = dout + row0 * H + h * 64;
+  T* dkbase = dqkv + row0 * ld + H + h * 64;
+  T* dvbase = dqkv + row0 * ld + 2 * H + h * 64;
 
   __shared__ __attribute__((aligned(16))) char k_lds[64 * 128];
   __shared__ __attribute__((aligned(16))) char v_lds[64 * 128];
@@ -518,17 +581,17 @@ void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
   const unsigned int seed32 = (unsigned int)(seed ^ (seed >> 32));
   const float inv_keep = DROP ? 1.f / (1.f - p) : 1.f;
 
-  stage64<T>(kbase, ld, kb * 64, S, k_lds);
-  stage64<T>(vbase, ld, kb * 64, S, v_lds);
-  stage64<T>(qbase, ld, 0, S, q_lds[0]);
-  stage64<T>(dobase, H, 0, S, do_lds[0]);
-  if (PRELOAD && S > 64) {
-    stage64<T>(qbase, ld, 64, S, q_lds[1]);
-    stage64<T>(dobase, H, 64, S, do_lds[1]);
+  stage64<T>(kbase, ld, kb * 64, len, k_lds);
+  stage64<T>(vbase, ld, kb * 64, len, v_lds);
+  stage64<T>(qbase, ld, 0, len, q_lds[0]);
+  stage64<T>(dobase, H, 0, len, do_lds[0]);
+  if (PRELOAD && len > 64) {
+    stage64<T>(qbase, ld, 64, len, q_lds[1]);
+    stage64<T>(dobase, H, 64, len, do_lds[1]);
   }
-  for (int i = threadIdx.x; i < S; i += NTHREADS) {
-    lse_lds[i] = lse[(long)bh * S + i];
-    dvec_lds[i] = dvec[(long)bh * S + i];
+  for (int i = threadIdx.x; i < len; i += NTHREADS) {
+    lse_lds[i] = lse[stat0 + i];
+    dvec_lds[i] = dvec[stat0 + i];
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -543,12 +606,12 @@ void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
   }
 
   f32x4 acc_dk[4] = {}, acc_dv[4] = {};
-  const int nt = S / 64;
+  const int nt = VARLEN ? (len + 63) / 64 : S / 64;
   int cur = 0;
   for (int t = 0; t < nt; ++t) {
     if (!PRELOAD && t + 1 < nt) {
-      stage64<T>(qbase, ld, (long)(t + 1) * 64, S, q_lds[cur ^ 1]);
-      stage64<T>(dobase, H, (long)(t + 1) * 64, S, do_lds[cur ^ 1]);
+      stage64<T>(qbase, ld, (long)(t + 1) * 64, len, q_lds[cur ^ 1]);
+      stage64<T>(dobase, H, (long)(t + 1) * 64, len, do_lds[cur ^ 1]);
     }
     // S^T = K @ Q^T and dP^T = V @ dO^T on this 64-query tile
     f32x4 acc_st[4] = {}, acc_dpt[4] = {};
@@ -574,11 +637,16 @@ void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
       for (int r = 0; r < 4; ++r) {
         const long gkey = kb * 64 + kr + (lane >> 4) * 4 + r;
         pt[j][r] = exp2f(acc_st[j][r] * scale2 + mv[r] - lse_j);
+        // tail query rows have no lse/dvec (lse_lds holds nothing there):
+        // their P^T is 0 by index, never by arithmetic on that slot
+        if (VARLEN && qrow >= len) pt[j][r] = 0.f;
         live[j][r] = true;
         if (DROP) {
+          const unsigned int grow =
+              VARLEN ? (unsigned int)(stat0 + qrow)
+                     : (unsigned int)bh * S + (unsigned int)qrow;
           const unsigned int rr = hash_rng32(
-              seed32, ((unsigned int)bh * S + (unsigned int)qrow) * S +
-                          (unsigned int)gkey);
+              seed32, drop_idx<VARLEN>(grow, (unsigned int)gkey, S));
           live[j][r] = (rr * 2.3283064365386963e-10f) >= p;
         }
       }
@@ -619,7 +687,8 @@ void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
         const long qrow = (long)t * 64 + j * 16 + (lane & 15);
         const float dvec_j = dvec_lds[qrow];
         const float dpt = live[j][r] ? acc_dpt[j][r] * inv_keep : 0.f;
-        const float dsv = pt[j][r] * (dpt - dvec_j) * scale;
+        float dsv = pt[j][r] * (dpt - dvec_j) * scale;
+        if (VARLEN && qrow >= len) dsv = 0.f;  // dvec_j is not data there
         const int qcol = j * 16 + (lane & 15);
         *reinterpret_cast<unsigned short*>(
             pds_lds + tr_addr(prow, qcol)) =
@@ -650,6 +719,7 @@ void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const long gkey = kb * 64 + kr + (lane >> 4) * 4 + r;
+    if (VARLEN && gkey >= len) continue;  // tail keys are never stored
 #pragma unroll
     for (int jd = 0; jd < 4; ++jd) {
       dkbase[gkey * ld + jd * 16 + ccol] = from_f32<T>(acc_dk[jd][r]);
@@ -685,24 +755,26 @@ static void check_fa_args(const torch::Tensor& qkv, const torch::Tensor& mask,
 }
 
 // launch macros live at file scope (a #define cannot appear inside a macro
-// argument — DISPATCH_FLOAT_TYPES takes the body as one)
+// argument — DISPATCH_FLOAT_TYPES takes the body as one). The call site
+// provides: S (padded sequence length; packed row count T under VARLEN),
+// seq_max (longest sequence: picks PRELOAD), has_mask/mask, cu_ptr.
 #define FA_FWD_L(PL)                                                           \
-  hipLaunchKernelGGL((fa_fwd_kernel<scalar_t, V8, HM, DR, PL>), grid,          \
+  hipLaunchKernelGGL((fa_fwd_kernel<scalar_t, V8, HM, DR, PL, VL>), grid,      \
                      dim3(NTHREADS), 0, stream,                                \
                      (const scalar_t*)qkv.data_ptr(),                          \
                      has_mask ? (const scalar_t*)mask.data_ptr() : nullptr,    \
                      (scalar_t*)o.data_ptr(), (float*)lse.data_ptr(),          \
                      seed_ptr, (unsigned long long)salt, (float)scale,         \
-                     (float)p, (int)nh, (int)S)
-#define FA_FWD(HMV, DRV)                                                       \
+                     (float)p, (int)nh, (int)S, cu_ptr)
+#define FA_FWD(HMV, DRV, VLV)                                                  \
   do {                                                                         \
-    constexpr bool HM = HMV, DR = DRV;                                         \
-    if (S <= 128) FA_FWD_L(true);                                              \
+    constexpr bool HM = HMV, DR = DRV, VL = VLV;                               \
+    if (seq_max <= 128) FA_FWD_L(true);                                        \
     else FA_FWD_L(false);                                                      \
   } while (0)
 
 #define FA_BWD_L(KERN, PL)                                                     \
-  hipLaunchKernelGGL((KERN<scalar_t, V8, HM, DR, PL>), grid,                   \
+  hipLaunchKernelGGL((KERN<scalar_t, V8, HM, DR, PL, VL>), grid,               \
                      dim3(NTHREADS), 0, stream,                                \
                      (const scalar_t*)dout.data_ptr(),                         \
                      (const scalar_t*)qkv.data_ptr(),                          \
@@ -712,11 +784,11 @@ static void check_fa_args(const torch::Tensor& qkv, const torch::Tensor& mask,
                      has_mask ? (const scalar_t*)mask.data_ptr() : nullptr,    \
                      (scalar_t*)dqkv.data_ptr(), seed_ptr,                     \
                      (unsigned long long)salt, (float)scale, (float)p,         \
-                     (int)nh, (int)S)
-#define FA_BWD(KERN, HMV, DRV)                                                 \
+                     (int)nh, (int)S, cu_ptr)
+#define FA_BWD(KERN, HMV, DRV, VLV)                                            \
   do {                                                                         \
-    constexpr bool HM = HMV, DR = DRV;                                         \
-    if (S <= 128) FA_BWD_L(KERN, true);                                        \
+    constexpr bool HM = HMV, DR = DRV, VL = VLV;                               \
+    if (seq_max <= 128) FA_BWD_L(KERN, true);                                  \
     else FA_BWD_L(KERN, false);                                                \
   } while (0)
 
@@ -727,6 +799,8 @@ std::vector<torch::Tensor> flash_attn_qkv_fwd(torch::Tensor qkv,
                                               long salt) {
   check_fa_args(qkv, mask, nh);
   const long B = qkv.size(0), S = qkv.size(1), H = (long)nh * 64;
+  const long seq_max = S;
+  const int* cu_ptr = nullptr;
   const bool has_mask = mask.defined() && mask.numel() > 0;
   const bool drop = p > 0.0;
   TORCH_CHECK(!drop || (seed_buf.defined() && seed_buf.is_cuda() &&
@@ -743,10 +817,10 @@ std::vector<torch::Tensor> flash_attn_qkv_fwd(torch::Tensor qkv,
     if constexpr (!std::is_same<scalar_t, float>::value) {
       using V8 = std::conditional_t<
           std::is_same<scalar_t, __hip_bfloat16>::value, bf16x8, f16x8>;
-      if (has_mask && drop) FA_FWD(true, true);
-      else if (has_mask) FA_FWD(true, false);
-      else if (drop) FA_FWD(false, true);
-      else FA_FWD(false, false);
+      if (has_mask && drop) FA_FWD(true, true, false);
+      else if (has_mask) FA_FWD(true, false, false);
+      else if (drop) FA_FWD(false, true, false);
+      else FA_FWD(false, false, false);
     } else {
       TORCH_CHECK(false, "flash_attn: fp32 not supported");
     }
@@ -760,6 +834,8 @@ torch::Tensor flash_attn_qkv_bwd(torch::Tensor dout, torch::Tensor qkv,
                                  double p, torch::Tensor seed_buf, long salt) {
   check_fa_args(qkv, mask, nh);
   const long B = qkv.size(0), S = qkv.size(1);
+  const long seq_max = S;
+  const int* cu_ptr = nullptr;
   const bool has_mask = mask.defined() && mask.numel() > 0;
   const bool drop = p > 0.0;
   auto dqkv = torch::empty_like(qkv);
@@ -776,20 +852,137 @@ torch::Tensor flash_attn_qkv_bwd(torch::Tensor dout, torch::Tensor qkv,
       // stages dO; O goes through the dS buffer) and consumed by dK/dV
       dim3 grid(S / 64, B * nh);
       if (has_mask && drop) {
-        FA_BWD(fa_bwd_dq_kernel, true, true);
-        FA_BWD(fa_bwd_dkv_kernel, true, true);
+        FA_BWD(fa_bwd_dq_kernel, true, true, false);
+        FA_BWD(fa_bwd_dkv_kernel, true, true, false);
       } else if (has_mask) {
-        FA_BWD(fa_bwd_dq_kernel, true, false);
-        FA_BWD(fa_bwd_dkv_kernel, true, false);
+        FA_BWD(fa_bwd_dq_kernel, true, false, false);
+        FA_BWD(fa_bwd_dkv_kernel, true, false, false);
       } else if (drop) {
-        FA_BWD(fa_bwd_dq_kernel, false, true);
-        FA_BWD(fa_bwd_dkv_kernel, false, true);
+        FA_BWD(fa_bwd_dq_kernel, false, true, false);
+        FA_BWD(fa_bwd_dkv_kernel, false, true, false);
       } else {
-        FA_BWD(fa_bwd_dq_kernel, false, false);
-        FA_BWD(fa_bwd_dkv_kernel, false, false);
+        FA_BWD(fa_bwd_dq_kernel, false, false, false);
+        FA_BWD(fa_bwd_dkv_kernel, false, false, false);
       }
     } else {
       TORCH_CHECK(false, "flash_attn: fp32 not supported");
+    }
+  });
+  return dqkv;
+}
+
+// ---------------------------------------------------------------------------
+// variable-length (padding-free) entry points: qkv [T, 3H] packed stream,
+// cu_seqlens int32 [B+1] on the device, max_seqlen known on the host (no
+// sync). Preconditions the host cannot check without a sync and the data
+// collate guarantees: cu_seqlens ascending from 0, every length in
+// [1, max_seqlen], cu_seqlens[B] <= T.
+// ---------------------------------------------------------------------------
+
+static void check_fa_varlen_args(const torch::Tensor& qkv,
+                                 const torch::Tensor& cu_seqlens,
+                                 long max_seqlen, long nh) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.is_contiguous() && qkv.dim() == 2,
+              "flash_attn_varlen: qkv must be contiguous [T, 3H]");
+  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16 ||
+                  qkv.scalar_type() == torch::kHalf,
+              "flash_attn_varlen: bf16/fp16 only");
+  TORCH_CHECK(qkv.size(1) == 3 * nh * 64,
+              "flash_attn_varlen: head_dim must be 64 and qkv last dim "
+              "3*nh*64");
+  TORCH_CHECK(qkv.size(0) > 0 && qkv.size(0) % 64 == 0,
+              "flash_attn_varlen: T must be a positive multiple of 64");
+  TORCH_CHECK(nh * qkv.size(0) <= (1L << 22),
+              "flash_attn_varlen: nh*T > 2^22 unsupported (32-bit dropout "
+              "counter)");
+  TORCH_CHECK(cu_seqlens.is_cuda() && cu_seqlens.is_contiguous() &&
+                  cu_seqlens.dim() == 1 && cu_seqlens.numel() >= 2 &&
+                  cu_seqlens.scalar_type() == torch::kInt,
+              "flash_attn_varlen: cu_seqlens must be a contiguous cuda int32 "
+              "[B+1]");
+  TORCH_CHECK(max_seqlen >= 1 && max_seqlen <= 1024,
+              "flash_attn_varlen: max_seqlen must be in [1, 1024] "
+              "(LDS-resident lse/dvec rows are sized for 1024)");
+}
+
+std::vector<torch::Tensor> flash_attn_varlen_fwd(torch::Tensor qkv,
+                                                 torch::Tensor cu_seqlens,
+                                                 long max_seqlen, long nh,
+                                                 double scale, double p,
+                                                 torch::Tensor seed_buf,
+                                                 long salt) {
+  check_fa_varlen_args(qkv, cu_seqlens, max_seqlen, nh);
+  const long S = qkv.size(0), B = cu_seqlens.numel() - 1, H = (long)nh * 64;
+  const long seq_max = max_seqlen;
+  const int* cu_ptr = (const int*)cu_seqlens.data_ptr();
+  const bool has_mask = false;
+  torch::Tensor mask;
+  const bool drop = p > 0.0;
+  TORCH_CHECK(!drop || (seed_buf.defined() && seed_buf.is_cuda() &&
+                        seed_buf.scalar_type() == torch::kLong),
+              "flash_attn_varlen: dropout needs a cuda int64 seed buffer");
+  // zero-filled: rows outside every sequence are never stored and the
+  // downstream dW GEMMs contract over all T rows
+  auto o = torch::zeros({S, H}, qkv.options());
+  auto lse = torch::empty({nh, S}, qkv.options().dtype(torch::kFloat));
+  dim3 grid((max_seqlen + 63) / 64, B * nh);
+  auto stream = at::hip::getCurrentHIPStream();
+  const auto* seed_ptr =
+      drop ? (const unsigned long long*)seed_buf.data_ptr() : nullptr;
+
+  DISPATCH_FLOAT_TYPES(qkv.scalar_type(), "flash_attn_varlen_fwd", [&] {
+    if constexpr (!std::is_same<scalar_t, float>::value) {
+      using V8 = std::conditional_t<
+          std::is_same<scalar_t, __hip_bfloat16>::value, bf16x8, f16x8>;
+      if (drop) FA_FWD(false, true, true);
+      else FA_FWD(false, false, true);
+    } else {
+      TORCH_CHECK(false, "flash_attn_varlen: fp32 not supported");
+    }
+  });
+  return {o, lse};
+}
+
+torch::Tensor flash_attn_varlen_bwd(torch::Tensor dout, torch::Tensor qkv,
+                                    torch::Tensor o, torch::Tensor lse,
+                                    torch::Tensor cu_seqlens, long max_seqlen,
+                                    long nh, double scale, double p,
+                                    torch::Tensor seed_buf, long salt) {
+  check_fa_varlen_args(qkv, cu_seqlens, max_seqlen, nh);
+  const long S = qkv.size(0), B = cu_seqlens.numel() - 1, H = (long)nh * 64;
+  TORCH_CHECK(dout.is_cuda() && dout.is_contiguous() &&
+                  dout.scalar_type() == qkv.scalar_type() &&
+                  dout.dim() == 2 && dout.size(0) == S && dout.size(1) == H,
+              "flash_attn_varlen: dout must be contiguous [T, H] of qkv "
+              "dtype");
+  TORCH_CHECK(o.is_contiguous() && o.sizes() == dout.sizes() &&
+                  lse.is_contiguous() && lse.numel() == nh * S,
+              "flash_attn_varlen: o [T, H] / lse [nh, T] from the forward");
+  const long seq_max = max_seqlen;
+  const int* cu_ptr = (const int*)cu_seqlens.data_ptr();
+  const bool has_mask = false;
+  torch::Tensor mask;
+  const bool drop = p > 0.0;
+  auto dqkv = torch::zeros_like(qkv);  // see flash_attn_varlen_fwd
+  auto dvec = torch::empty({nh, S}, qkv.options().dtype(torch::kFloat));
+  dim3 grid((max_seqlen + 63) / 64, B * nh);
+  auto stream = at::hip::getCurrentHIPStream();
+  const auto* seed_ptr =
+      drop ? (const unsigned long long*)seed_buf.data_ptr() : nullptr;
+
+  DISPATCH_FLOAT_TYPES(qkv.scalar_type(), "flash_attn_varlen_bwd", [&] {
+    if constexpr (!std::is_same<scalar_t, float>::value) {
+      using V8 = std::conditional_t<
+          std::is_same<scalar_t, __hip_bfloat16>::value, bf16x8, f16x8>;
+      if (drop) {
+        FA_BWD(fa_bwd_dq_kernel, false, true, true);
+        FA_BWD(fa_bwd_dkv_kernel, false, true, true);
+      } else {
+        FA_BWD(fa_bwd_dq_kernel, false, false, true);
+        FA_BWD(fa_bwd_dkv_kernel, false, false, true);
+      }
+    } else {
+      TORCH_CHECK(false, "flash_attn_varlen: fp32 not supported");
     }
   });
   return dqkv;

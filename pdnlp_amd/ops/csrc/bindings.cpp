@@ -80,6 +80,17 @@ torch::Tensor flash_attn_qkv_bwd(torch::Tensor dout, torch::Tensor qkv,
                                  torch::Tensor o, torch::Tensor lse,
                                  torch::Tensor mask, long nh, double scale,
                                  double p, torch::Tensor seed_buf, long salt);
+std::vector<torch::Tensor> flash_attn_varlen_fwd(torch::Tensor qkv,
+                                                 torch::Tensor cu_seqlens,
+                                                 long max_seqlen, long nh,
+                                                 double scale, double p,
+                                                 torch::Tensor seed_buf,
+                                                 long salt);
+torch::Tensor flash_attn_varlen_bwd(torch::Tensor dout, torch::Tensor qkv,
+                                    torch::Tensor o, torch::Tensor lse,
+                                    torch::Tensor cu_seqlens, long max_seqlen,
+                                    long nh, double scale, double p,
+                                    torch::Tensor seed_buf, long salt);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_fwd", &layernorm_fwd);
@@ -113,4 +124,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_nt_fwd", &gemm_nt_fwd);
   m.def("flash_attn_qkv_fwd", &flash_attn_qkv_fwd);
   m.def("flash_attn_qkv_bwd", &flash_attn_qkv_bwd);
+  m.def("flash_attn_varlen_fwd", &flash_attn_varlen_fwd);
+  m.def("flash_attn_varlen_bwd", &flash_attn_varlen_bwd);
 }

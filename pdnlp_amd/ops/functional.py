@@ -493,6 +493,67 @@ def attention_packed(qkv: torch.Tensor, mask: Optional[torch.Tensor],
     return ctx.transpose(1, 2).reshape(B, S, H)
 
 
+class _FlashAttnVarlenFn(torch.autograd.Function):
+    """Flash attention over a packed token stream [T, 3H] whose sequence
+    boundaries are ``cu_seqlens`` — the padding-free counterpart of
+    _FlashAttnQKVFn (same kernels, VARLEN instantiations). Rows outside
+    every sequence come back exactly zero in the output and in dqkv."""
+
+    @staticmethod
+    def forward(ctx, qkv, cu_seqlens, max_seqlen, nh, scale, p_drop):
+        if p_drop > 0.0:
+            seed_buf, salt = _dropout_seed.get(qkv.device)
+        else:
+            seed_buf, salt = torch.Tensor(), 0
+        o, lse = ext().flash_attn_varlen_fwd(qkv, cu_seqlens, max_seqlen, nh,
+                                             scale, p_drop, seed_buf, salt)
+        ctx.save_for_backward(qkv, o, lse, cu_seqlens,
+                              seed_buf if p_drop > 0.0 else torch.Tensor())
+        ctx.max_seqlen = max_seqlen
+        ctx.nh, ctx.scale, ctx.p, ctx.salt = nh, scale, p_drop, salt
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, lse, cu_seqlens, seed_buf = ctx.saved_tensors
+        dqkv = ext().flash_attn_varlen_bwd(
+            do.contiguous(), qkv, o, lse, cu_seqlens, ctx.max_seqlen, ctx.nh,
+            ctx.scale, ctx.p, seed_buf, ctx.salt)
+        return dqkv, None, None, None, None, None
+
+
+def attention_varlen(qkv: torch.Tensor, cu_seqlens: torch.Tensor,
+                     max_seqlen: int, num_heads: int, dropout_p: float = 0.0,
+                     training: bool = False) -> torch.Tensor:
+    """Attention on a packed (padding-free) QKV projection output.
+
+    qkv: [T, 3H]; sequence b occupies rows cu_seqlens[b]..cu_seqlens[b+1]
+    (int32 [B+1]); T >= cu_seqlens[B]. ``max_seqlen`` is the longest
+    sequence as a host int. Returns the context [T, H]; rows outside every
+    sequence are exactly zero, forward and backward. On a ROCm GPU with
+    head_dim 64, T%64==0 and bf16/fp16 this runs the fused MFMA flash
+    kernel; otherwise a per-sequence loop over :func:`attention` (which
+    reads cu_seqlens on the host)."""
+    T, H3 = qkv.shape
+    H = H3 // 3
+    hd = H // num_heads
+    p_eff = float(dropout_p if training else 0.0)
+    if hip_enabled(qkv) and hd == 64 and T % 64 == 0 \
+            and qkv.dtype in (torch.bfloat16, torch.float16):
+        return _FlashAttnVarlenFn.apply(
+            qkv.contiguous(), cu_seqlens.contiguous(), int(max_seqlen),
+            num_heads, 1.0 / math.sqrt(hd), p_eff)
+    bounds = cu_seqlens.tolist()
+    outs = []
+    for s0, s1 in zip(bounds[:-1], bounds[1:]):
+        q, k, v = (t.view(1, s1 - s0, num_heads, hd).transpose(1, 2)
+                   for t in qkv[s0:s1].split(H, dim=-1))
+        c = attention(q, k, v, None, p_eff, training)
+        outs.append(c.transpose(1, 2).reshape(s1 - s0, H))
+    outs.append(qkv.new_zeros(T - bounds[-1], H))
+    return torch.cat(outs, dim=0)
+
+
 # --------------------------------------------------------------------------
 # Bias + dropout + residual + LayerNorm (K6/K8 epilogue)
 # --------------------------------------------------------------------------

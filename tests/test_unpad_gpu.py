@@ -1,0 +1,382 @@
+"""Padding-free path (``--unpad``) on the GPU: the variable-length flash
+attention kernels against an fp32 per-sequence torch reference and against
+the shipped padded kernel, the dropout realisation, and the packed model /
+Trainer / AMP wiring on the HIP path."""
+
+import functools
+import math
+
+import pytest
+import torch
+
+pytestmark = [pytest.mark.gpu, pytest.mark.timeout(600)]
+
+DEV = "cuda:0"
+NH, HD = 2, 64
+H = NH * HD
+SCALE = 1.0 / math.sqrt(HD)
+FWD_TOL = dict(rtol=3e-2, atol=3e-2)   # as test_flash_attn_fwd
+BWD_TOL = dict(rtol=5e-2, atol=5e-2)   # as test_flash_attn_bwd
+
+
+def ext():
+    from pdnlp_amd.ops import ext as _ext
+    e = _ext()
+    assert e is not None, "HIP extension must be built on the GPU box"
+    return e
+
+
+def _cu(lens):
+    cu = [0]
+    for n in lens:
+        cu.append(cu[-1] + n)
+    return cu
+
+
+def _round64(n):
+    return (n + 63) // 64 * 64
+
+
+def _nan_prefill(*shape, dtype):
+    """Allocate and free a NaN block of the output's size: the caching
+    allocator tends to hand the same block to the next request, so an output
+    that is not zero-filled shows up as NaN."""
+    x = torch.full(shape, float("nan"), device=DEV, dtype=dtype)
+    del x
+
+
+def _ref_attn(qkv32, cu, keep=None, p=0.0):
+    """fp32 per-sequence attention on a packed [T, 3H] stream; rows outside
+    the sequences are 0. ``keep`` (per sequence [NH, n, n] bool) applies a
+    given dropout mask."""
+    T = qkv32.shape[0]
+    out = qkv32.new_zeros(T, H)
+    for b, (s0, s1) in enumerate(zip(cu[:-1], cu[1:])):
+        n = s1 - s0
+        q, k, v = (t.reshape(n, NH, HD).transpose(0, 1)
+                   for t in qkv32[s0:s1].split(H, dim=-1))
+        pr = torch.softmax(q @ k.transpose(-1, -2) * SCALE, dim=-1)
+        if keep is not None:
+            pr = pr * keep[b] / (1.0 - p)
+        out[s0:s1] = (pr @ v).transpose(0, 1).reshape(n, H)
+    return out
+
+
+LENGTH_SETS = {
+    "one-token": ([1], None),
+    "one-tile": ([64], None),
+    "tile-plus-one": ([65], None),
+    "mixed-preload": ([63, 1, 128, 17], None),
+    "streamed-midtile": ([129, 64, 200], None),   # the non-PRELOAD path
+    "dummy-tail-tile": ([64, 64], 192),           # a whole tile of no one's
+}
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("case", list(LENGTH_SETS))
+def test_varlen_kernel_fwd_bwd(case, dtype):
+    e = ext()
+    lens, T = LENGTH_SETS[case]
+    cu = _cu(lens)
+    total = cu[-1]
+    T = T or _round64(total)
+    torch.manual_seed(0)
+    qkv = torch.randn(T, 3 * H, device=DEV, dtype=dtype)
+    dout = torch.randn(T, H, device=DEV, dtype=dtype)
+    cu_t = torch.tensor(cu, dtype=torch.int32, device=DEV)
+    mx = max(lens)
+
+    _nan_prefill(T, H, dtype=dtype)
+    o, lse = e.flash_attn_varlen_fwd(qkv, cu_t, mx, NH, SCALE, 0.0,
+                                     torch.Tensor(), 0)
+    assert o.shape == (T, H) and lse.shape == (NH, T)
+    assert torch.isfinite(o).all()
+    assert (o[total:] == 0).all(), "rows outside the sequences must be 0"
+    q32 = qkv.float().requires_grad_()
+    ref = _ref_attn(q32, cu)
+    torch.testing.assert_close(o.float(), ref.detach(), **FWD_TOL)
+    # lse of the real rows is data (natural-log-free check: finite)
+    for h in range(NH):
+        assert torch.isfinite(lse[h, :total]).all()
+
+    _nan_prefill(T, 3 * H, dtype=dtype)
+    dqkv = e.flash_attn_varlen_bwd(dout, qkv, o, lse, cu_t, mx, NH, SCALE,
+                                   0.0, torch.Tensor(), 0)
+    assert dqkv.shape == (T, 3 * H)
+    assert torch.isfinite(dqkv).all()
+    assert (dqkv[total:] == 0).all(), "rows outside the sequences must be 0"
+    ref.backward(dout.float())
+    torch.testing.assert_close(dqkv.float(), q32.grad, **BWD_TOL)
+
+
+def test_varlen_rejects_bad_arguments():
+    e = ext()
+    qkv = torch.randn(64, 3 * H, device=DEV, dtype=torch.bfloat16)
+    cu = torch.tensor([0, 10], dtype=torch.int32, device=DEV)
+    none = torch.Tensor()
+    for bad_max in (0, 1025):
+        with pytest.raises(RuntimeError, match="max_seqlen"):
+            e.flash_attn_varlen_fwd(qkv, cu, bad_max, NH, SCALE, 0.0, none, 0)
+    with pytest.raises(RuntimeError, match="multiple of 64"):
+        e.flash_attn_varlen_fwd(qkv[:32].contiguous(), cu, 10, NH, SCALE,
+                                0.0, none, 0)
+    with pytest.raises(RuntimeError, match="int32"):
+        e.flash_attn_varlen_fwd(qkv, cu.long(), 10, NH, SCALE, 0.0, none, 0)
+    with pytest.raises(RuntimeError, match="bf16/fp16"):
+        e.flash_attn_varlen_fwd(qkv.float(), cu, 10, NH, SCALE, 0.0, none, 0)
+
+
+def test_varlen_agrees_with_padded_kernel():
+    """The same sequences through attention_packed (additive mask, S=128)
+    and through attention_varlen: real rows and their gradients agree."""
+    from pdnlp_amd import ops
+    lens, S = [63, 1, 128, 17], 128
+    cu = _cu(lens)
+    total, B = cu[-1], len(lens)
+    T = _round64(total)
+    dtype = torch.bfloat16
+    torch.manual_seed(1)
+    qkv = torch.randn(T, 3 * H, device=DEV, dtype=dtype)
+    dout = torch.randn(T, H, device=DEV, dtype=dtype)
+    cu_t = torch.tensor(cu, dtype=torch.int32, device=DEV)
+
+    qv = qkv.clone().requires_grad_()
+    ov = ops.attention_varlen(qv, cu_t, max(lens), NH)
+    ov.backward(dout)
+
+    qp = torch.zeros(B, S, 3 * H, device=DEV, dtype=dtype)
+    dp = torch.zeros(B, S, H, device=DEV, dtype=dtype)
+    keep = torch.zeros(B, S, device=DEV)
+    for b, n in enumerate(lens):
+        qp[b, :n] = qkv[cu[b]:cu[b + 1]]
+        dp[b, :n] = dout[cu[b]:cu[b + 1]]
+        keep[b, :n] = 1
+    mask = ((1.0 - keep[:, None, None, :]) * -10000.0).to(dtype)
+    qp.requires_grad_()
+    op = ops.attention_packed(qp, mask, NH)
+    op.backward(dp)
+    for b, n in enumerate(lens):
+        sl = slice(cu[b], cu[b + 1])
+        torch.testing.assert_close(ov[sl].float(), op[b, :n].float(),
+                                   **FWD_TOL)
+        torch.testing.assert_close(qv.grad[sl].float(),
+                                   qp.grad[b, :n].float(), **BWD_TOL)
+
+
+def _recover_probs(e, qkv, cu, cu_t, mx, p, seed, salt):
+    """Per sequence [NH, n, n]: the (dropped, rescaled) probabilities the
+    kernel applies, read out by running it with V = basis vectors of one
+    64-key chunk at a time (then O = P[:, chunk])."""
+    T = qkv.shape[0]
+    out = []
+    for b, (s0, s1) in enumerate(zip(cu[:-1], cu[1:])):
+        n = s1 - s0
+        pm = torch.zeros(NH, n, n, device=DEV)
+        for c in range((n + 63) // 64):
+            k0, k1 = c * 64, min(c * 64 + 64, n)
+            probe = qkv.clone()
+            probe[:, 2 * H:] = 0
+            eye = torch.eye(64, device=DEV, dtype=qkv.dtype)[:k1 - k0]
+            for h in range(NH):
+                probe[s0 + k0:s0 + k1,
+                      2 * H + h * HD:2 * H + (h + 1) * HD] = eye
+            o, _ = e.flash_attn_varlen_fwd(probe, cu_t, mx, NH, SCALE, p,
+                                           seed, salt)
+            pm[:, :, k0:k1] = o[s0:s1].float().reshape(
+                n, NH, HD).transpose(0, 1)[:, :, :k1 - k0]
+        out.append(pm)
+    return out
+
+
+def test_varlen_dropout():
+    e = ext()
+    lens, p = [65, 17], 0.1
+    cu = _cu(lens)
+    total = cu[-1]
+    T = _round64(total)
+    dtype = torch.bfloat16
+    torch.manual_seed(2)
+    qkv = torch.randn(T, 3 * H, device=DEV, dtype=dtype)
+    dout = torch.randn(T, H, device=DEV, dtype=dtype)
+    cu_t = torch.tensor(cu, dtype=torch.int32, device=DEV)
+    mx = max(lens)
+    seed = torch.tensor([1234], dtype=torch.int64, device=DEV)
+    none = torch.Tensor()
+
+    o1, lse = e.flash_attn_varlen_fwd(qkv, cu_t, mx, NH, SCALE, p, seed, 7)
+    o2, _ = e.flash_attn_varlen_fwd(qkv, cu_t, mx, NH, SCALE, p, seed, 7)
+    assert torch.equal(o1, o2)            # same (seed, salt): bit-identical
+    seed2 = torch.tensor([4321], dtype=torch.int64, device=DEV)
+    o3, _ = e.flash_attn_varlen_fwd(qkv, cu_t, mx, NH, SCALE, p, seed2, 7)
+    assert not torch.equal(o1, o3)        # a reseed changes the masks
+    assert (o1[total:] == 0).all()
+
+    pd = _recover_probs(e, qkv, cu, cu_t, mx, p, seed, 7)
+    p0 = _recover_probs(e, qkv, cu, cu_t, mx, 0.0, none, 0)
+    keep = [(a != 0) | (b0 == 0) for a, b0 in zip(pd, p0)]
+    n_all = sum(k.numel() for k in keep)
+    drop_rate = 1.0 - sum(k.sum().item() for k in keep) / n_all
+    print(f"varlen dropout: drop rate {drop_rate:.4f} over {n_all} entries")
+    assert abs(drop_rate - p) < 0.05
+
+    # forward and backward against the fp32 reference under the SAME mask
+    q32 = qkv.float().requires_grad_()
+    ref = _ref_attn(q32, cu, keep=[k.float() for k in keep], p=p)
+    torch.testing.assert_close(o1.float(), ref.detach(), **FWD_TOL)
+    dqkv = e.flash_attn_varlen_bwd(dout, qkv, o1, lse, cu_t, mx, NH, SCALE,
+                                   p, seed, 7)
+    ref.backward(dout.float())
+    assert torch.isfinite(dqkv).all() and (dqkv[total:] == 0).all()
+    torch.testing.assert_close(dqkv.float(), q32.grad, **BWD_TOL)
+
+
+# ------------------------------------------------------------------- model
+MODEL_LENGTHS = {
+    "T320": [5, 64, 1, 33, 128, 70],
+    "T704": [128, 128, 128, 128, 100, 60, 17, 3],
+}
+
+# Packed-vs-padded bound, as max|a-b| / max(std|ref|, 1) per tensor: twice
+# the distance of the padded HIP run from the fp32 CPU reference, measured
+# on these very inputs (MI355X, bf16; worst tensor of each length set).
+# Packed-vs-padded itself measured 3.8e-06 on both sets.
+MEASURED_PADDED_VS_FP32 = {"T320": 1.622e-03, "T704": 1.480e-03}
+PACKED_VS_PADDED_BOUND = {k: 2 * v for k, v in MEASURED_PADDED_VS_FP32.items()}
+
+
+def _model_cfg():
+    from pdnlp_amd.config import BertConfig
+    return BertConfig(vocab_size=1024, hidden_size=256, num_hidden_layers=2,
+                      num_attention_heads=4, intermediate_size=1024,
+                      hidden_dropout_prob=0.0,
+                      attention_probs_dropout_prob=0.0)
+
+
+def _run(model, device, **inputs):
+    model.zero_grad(set_to_none=True)
+    out = model(**{k: (v.to(device) if torch.is_tensor(v) else v)
+                   for k, v in inputs.items()})
+    out.loss.backward()
+    res = {"logits": out.logits.detach().float().cpu()}
+    for n, p in model.named_parameters():
+        res[n] = p.grad.detach().float().cpu()
+    return res
+
+
+def _rel(a, b, ref):
+    return (a - b).abs().max().item() / max(ref.abs().std().item(), 1.0)
+
+
+@functools.lru_cache(maxsize=None)
+def _model_runs(name):
+    """(fp32 CPU padded reference, HIP padded, HIP packed) logits and
+    parameter gradients for one length set; same bf16-representable
+    weights everywhere."""
+    import copy
+    from pdnlp_amd.data import pack_batch
+    from pdnlp_amd.models import BertForSequenceClassification
+    lens = MODEL_LENGTHS[name]
+    torch.manual_seed(123)
+    gpu_model = BertForSequenceClassification(_model_cfg()).to(torch.bfloat16)
+    cpu_model = copy.deepcopy(gpu_model).float().train()
+    gpu_model = gpu_model.to(DEV).train()
+    g = torch.Generator().manual_seed(5)
+    B, S = len(lens), 128
+    mask = (torch.arange(S)[None, :] < torch.tensor(lens)[:, None]).long()
+    ids = torch.randint(106, 1024, (B, S), generator=g) * mask
+    batch = {"input_ids": ids, "attention_mask": mask,
+             "token_type_ids": torch.zeros_like(ids),
+             "label": torch.randint(0, 6, (B,), generator=g)}
+    padded_in = dict(input_ids=ids, attention_mask=mask,
+                     token_type_ids=batch["token_type_ids"],
+                     labels=batch["label"])
+    p = pack_batch(batch)
+    assert p["input_ids"].numel() == int(name[1:])
+    packed_in = dict(input_ids=p["input_ids"],
+                     token_type_ids=p["token_type_ids"], labels=p["label"],
+                     cu_seqlens=p["cu_seqlens"], max_seqlen=p["max_seqlen"],
+                     position_ids=p["position_ids"])
+    return (_run(cpu_model, "cpu", **padded_in),
+            _run(gpu_model, DEV, **padded_in),
+            _run(gpu_model, DEV, **packed_in))
+
+
+@pytest.mark.parametrize("name", list(MODEL_LENGTHS))
+def test_model_packed_matches_padded_hip(name):
+    ref, padded, packed = _model_runs(name)
+    worst_ref = worst = 0.0
+    for k in ref:
+        e_ref = _rel(padded[k], ref[k], ref[k])
+        e_pk = _rel(packed[k], padded[k], ref[k])
+        worst_ref, worst = max(worst_ref, e_ref), max(worst, e_pk)
+        print(f"{name} {k}: padded-vs-fp32 {e_ref:.3e}  "
+              f"packed-vs-padded {e_pk:.3e}")
+    print(f"{name} WORST padded-vs-fp32 {worst_ref:.3e}  "
+          f"packed-vs-padded {worst:.3e}")
+    for k in ref:
+        assert torch.isfinite(packed[k]).all(), k
+        assert _rel(packed[k], padded[k], ref[k]) \
+            <= PACKED_VS_PADDED_BOUND[name], k
+
+
+# ---------------------------------------------------------- Trainer and AMP
+def _unpad_training(tmp_path, amp_dtype, epochs, n=16):
+    from torch.utils.data import DataLoader
+    from pdnlp_amd.config import Args
+    from pdnlp_amd.data import Collate, SyntheticClsDataset
+    from pdnlp_amd.engine.trainer import build_training
+    from pdnlp_amd.models import BertForSequenceClassification
+    from pdnlp_amd.utils import set_seed
+    set_seed(123)
+    args = Args()
+    args.strategy = "single"
+    args.unpad = True
+    args.amp, args.amp_dtype = True, amp_dtype
+    args.init_scale = 1024.0
+    args.learning_rate = 5e-4
+    args.epochs = epochs
+    args.do_dev = False
+    args.log_every = 100
+    args.output_dir = str(tmp_path)
+    args.ckpt_path = str(tmp_path / "model.pt")
+    cfg = _model_cfg()
+    cfg.hidden_dropout_prob = cfg.attention_probs_dropout_prob = 0.1
+    model, opt, scaler, trainer = build_training(
+        args, model=BertForSequenceClassification(cfg))
+    # one batch per epoch, lengths 8..128, label = bucket of the 2nd token
+    ds = SyntheticClsDataset(n, seq_len=128, vocab_size=cfg.vocab_size,
+                             var_len=True)
+    loader = DataLoader(ds, batch_size=n, shuffle=False,
+                        collate_fn=Collate(None, 128, unpad=True))
+    losses = []
+    orig = trainer.on_step
+
+    def spy(batch):
+        assert "cu_seqlens" in batch and batch["input_ids"].dim() == 1
+        res = orig(batch)
+        losses.append(res[0].detach())
+        return res
+
+    trainer.on_step = spy
+    before = [p.detach().clone() for p in model.parameters()]
+    trainer.train(loader)
+    return [l.item() for l in losses], before, model, scaler
+
+
+def test_trainer_unpad_bf16_loss_decreases(tmp_path):
+    losses, _, model, scaler = _unpad_training(tmp_path, "bf16", epochs=4)
+    print("unpad bf16 trainer losses:", losses)
+    assert scaler is None and len(losses) == 4
+    assert all(math.isfinite(l) for l in losses), losses
+    assert losses[3] < losses[0], losses
+
+
+def test_unpad_fp16_grad_scaler_step(tmp_path):
+    losses, before, model, scaler = _unpad_training(tmp_path, "fp16",
+                                                    epochs=1)
+    assert scaler is not None and len(losses) == 1
+    assert math.isfinite(losses[0])
+    assert scaler.get_scale() == 1024.0      # no overflow: the step applied
+    changed = sum(not torch.equal(b, p.data)
+                  for b, p in zip(before, model.parameters()))
+    assert changed > 0, "the fp16 + GradScaler step must update the weights"

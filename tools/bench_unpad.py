@@ -1,0 +1,181 @@
+#!/usr/bin/env python
+"""Padded vs padding-free (``--unpad``) training steps on real-data lengths.
+
+    python tools/bench_unpad.py [--pairs 5] [--steps 30] [--multiple 64]
+
+Eager bf16 BERT-base training steps (forward, backward, fused AdamW) at
+batch 32, once on padded [32, 128] batches and once on the same batches
+packed by ``pack_batch``. Sequence lengths come from ``data/train.json``
+when present (characters after space-strip plus [CLS]/[SEP], capped at
+128), otherwise from a seeded synthetic sample clipped to [3, 128] with
+median ~15 and mean ~20 — the statistics of the reference dataset's first
+10 000 samples.
+
+Method: a fixed pool of seeded batches lives on the device; every batch of
+the pool runs once per mode before timing (each distinct packed length T is
+a new shape). Timed windows of ``--steps`` steps alternate padded / unpad,
+``--pairs`` times, each window closed by a device synchronise. The tool
+reports every window, the range per mode and whether the ranges are
+disjoint, then ``torch.cuda.memory_reserved()`` after ``--mem-steps`` steps
+per mode (allocator cache emptied in between), and one JSON line.
+"""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pdnlp_amd.data import load_data, pack_batch  # noqa: E402
+from pdnlp_amd.models import build_model  # noqa: E402
+from pdnlp_amd.ops.adamw import build_optimizer  # noqa: E402
+from pdnlp_amd.utils import set_seed  # noqa: E402
+
+S, VOCAB = 128, 21128
+
+
+def lengths(n, seed, data_path):
+    if os.path.isfile(data_path):
+        data = load_data(data_path, limit=10000)
+        lens = [min(len(t.replace(" ", "")) + 2, S) for t, _ in data]
+        g = torch.Generator().manual_seed(seed)
+        pick = torch.randint(0, len(lens), (n,), generator=g)
+        return f"real lengths from {data_path}", [lens[i] for i in pick]
+    # lognormal: median exp(mu) = 15, mean exp(mu + sigma^2/2) = 20
+    g = torch.Generator().manual_seed(seed)
+    mu, sigma = math.log(15.0), math.sqrt(2.0 * math.log(20.0 / 15.0))
+    x = torch.exp(mu + sigma * torch.randn(n, generator=g))
+    return ("synthetic lognormal lengths (median ~15, mean ~20)",
+            x.round().clamp(3, S).long().tolist())
+
+
+def make_batches(lens, batch, seed):
+    g = torch.Generator().manual_seed(seed + 1)
+    out = []
+    for i in range(0, len(lens), batch):
+        ll = torch.tensor(lens[i:i + batch])
+        mask = (torch.arange(S)[None, :] < ll[:, None]).long()
+        ids = torch.randint(106, VOCAB, (batch, S), generator=g)
+        ids[:, 0] = 101
+        ids[torch.arange(batch), ll - 1] = 102
+        out.append({"input_ids": ids * mask, "attention_mask": mask,
+                    "token_type_ids": torch.zeros_like(ids),
+                    "label": torch.randint(0, 6, (batch,), generator=g)})
+    return out
+
+
+def to_device(b, dev):
+    return {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in b.items()}
+
+
+class Mode:
+    def __init__(self, name, batches, dev):
+        set_seed(123)
+        self.name = name
+        self.model = build_model("bert-base").to(torch.bfloat16).to(dev)
+        self.model.train()
+        self.opt = build_optimizer(self.model, lr=3e-5)
+        self.batches = batches
+        self.i = 0
+
+    def step(self):
+        b = self.batches[self.i % len(self.batches)]
+        self.i += 1
+        if "cu_seqlens" in b:
+            out = self.model(
+                input_ids=b["input_ids"], token_type_ids=b["token_type_ids"],
+                labels=b["label"], cu_seqlens=b["cu_seqlens"],
+                max_seqlen=b["max_seqlen"], position_ids=b["position_ids"])
+        else:
+            out = self.model(
+                input_ids=b["input_ids"], attention_mask=b["attention_mask"],
+                token_type_ids=b["token_type_ids"], labels=b["label"])
+        out.loss.backward()
+        self.opt.step()
+        self.opt.zero_grad(set_to_none=True)
+        return out.loss
+
+    def window(self, steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            loss = self.step()
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3 / steps
+        assert math.isfinite(loss.item()), f"{self.name}: loss {loss.item()}"
+        return ms
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--pool", type=int, default=40, help="distinct batches")
+    ap.add_argument("--pairs", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--mem-steps", type=int, default=200)
+    ap.add_argument("--multiple", type=int, default=64)
+    ap.add_argument("--seed", type=int, default=123)
+    ap.add_argument("--data-path", default="./data/train.json")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_unpad.py measures GPU step time: no GPU visible")
+    dev = torch.device("cuda:0")
+
+    source, lens = lengths(a.pool * a.batch, a.seed, a.data_path)
+    padded = make_batches(lens, a.batch, a.seed)
+    packed = [pack_batch(b, multiple=a.multiple) for b in padded]
+    toks = [int(b["cu_seqlens"][-1]) for b in packed]
+    rows = [b["input_ids"].numel() for b in packed]
+    print(f"lengths: {source}; mean {sum(lens) / len(lens):.1f}, median "
+          f"{sorted(lens)[len(lens) // 2]}")
+    print(f"batch {a.batch}: mean real tokens {sum(toks) / len(toks):.0f}, "
+          f"mean packed rows (multiple {a.multiple}) "
+          f"{sum(rows) / len(rows):.0f} (max {max(rows)}, "
+          f"{len(set(rows))} distinct) vs {a.batch * S} padded rows")
+
+    modes = [Mode("padded", [to_device(b, dev) for b in padded], dev),
+             Mode("unpad", [to_device(b, dev) for b in packed], dev)]
+    for m in modes:                      # every shape of the pool, once
+        m.window(len(m.batches))
+    times = {m.name: [] for m in modes}
+    for p in range(a.pairs):
+        for m in modes:
+            times[m.name].append(m.window(a.steps))
+        print(f"pair {p}: padded {times['padded'][-1]:.3f} ms/step, "
+              f"unpad {times['unpad'][-1]:.3f} ms/step")
+    rng = {k: (min(v), max(v)) for k, v in times.items()}
+    disjoint = rng["unpad"][1] < rng["padded"][0]
+    for k, (lo, hi) in rng.items():
+        print(f"{k}: {lo:.3f} .. {hi:.3f} ms/step over {a.pairs} windows "
+              f"of {a.steps} steps")
+    print("ranges disjoint in favour of unpad:", disjoint)
+
+    reserved = {}
+    for m in modes:
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        base = torch.cuda.memory_reserved()
+        m.window(a.mem_steps // 2)
+        mid = torch.cuda.memory_reserved()
+        m.window(a.mem_steps - a.mem_steps // 2)
+        reserved[m.name] = {"start": base, "half": mid,
+                            "end": torch.cuda.memory_reserved()}
+        print(f"{m.name}: memory_reserved {base / 2**20:.0f} MiB at start, "
+              f"{mid / 2**20:.0f} MiB after {a.mem_steps // 2} steps, "
+              f"{reserved[m.name]['end'] / 2**20:.0f} MiB after "
+              f"{a.mem_steps}")
+    print(json.dumps({
+        "metric": "bench_unpad", "source": source, "batch": a.batch,
+        "multiple": a.multiple, "mean_tokens": sum(toks) / len(toks),
+        "mean_rows": sum(rows) / len(rows), "ms_per_step": times,
+        "range_ms": rng, "disjoint": disjoint,
+        "speedup_of_medians": sorted(times["padded"])[a.pairs // 2]
+        / sorted(times["unpad"])[a.pairs // 2],
+        "memory_reserved": reserved}))
+
+
+if __name__ == "__main__":
+    main()
