@@ -112,7 +112,12 @@ class GradScaler:
             self._found_val = bool(self._found_dev.item() != 0)
         return bool(self._found_val)
 
-    def step(self, optimizer, *args, **kwargs):
+    def step(self, optimizer, *args, grad_coef=None, **kwargs):
+        """``grad_coef``: optional fp32[1] device clip coefficient, computed
+        by the caller on the UNSCALED gradients (``unscale_`` first) and
+        forwarded to the optimizer on both paths."""
+        if grad_coef is not None:
+            kwargs["grad_coef"] = grad_coef
         if not self.enabled:
             return optimizer.step(*args, **kwargs)
         self.unscale_(optimizer)
@@ -120,6 +125,9 @@ class GradScaler:
             from ..ops.adamw import FusedAdamW
             if isinstance(optimizer, FusedAdamW):
                 # overflow skip happens INSIDE the AdamW kernel — no sync
+                if grad_coef is not None:
+                    return optimizer.step(found_inf=self._found_dev,
+                                          grad_coef=grad_coef)
                 return optimizer.step(found_inf=self._found_dev)
         if self._found_inf:
             return None  # skip the step on overflow

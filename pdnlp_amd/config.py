@@ -120,7 +120,12 @@ class Args:
     adam_beta1: float = 0.9
     adam_beta2: float = 0.999
     adam_eps: float = 1e-8
-    max_grad_norm: float = 0.0         # 0 = off (reference does not clip)
+    # global-norm gradient clipping, 0 = off (the reference's own loops do
+    # not clip; its HF-Trainer entrypoint does, at HF's default 1.0). The
+    # norm is one device-side read pass and the coefficient rides into the
+    # optimizer kernels — no host sync, gradients not rewritten; under
+    # zero/hooks it is taken on the averaged gradient inside step().
+    max_grad_norm: float = 0.0
     grad_accum_steps: int = 1
     optimizer: str = "adamw"           # "adamw" | "sgd" (fabric alt-path)
     sgd_momentum: float = 0.9

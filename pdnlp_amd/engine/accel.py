@@ -20,6 +20,15 @@ from ..parallel.bootstrap import init_distributed
 from ..parallel.ddp import DistributedDataParallel
 
 
+
+class _GradHolder:
+    """What ``GradScaler.unscale_`` walks: an optimizer-shaped view of a
+    parameter list."""
+
+    def __init__(self, params):
+        self.param_groups = [{"params": list(params)}]
+
+
 class Accelerator:
     def __init__(self, mixed_precision: Optional[str] = None,
                  gradient_accumulation_steps: int = 1,
@@ -59,6 +68,7 @@ class Accelerator:
         if dist.is_initialized():
             model = DistributedDataParallel(model,
                                             bucket_cap_mb=self.bucket_cap_mb)
+        self._model = model
         return model
 
     def _prepare_loader(self, loader: DataLoader) -> DataLoader:
@@ -92,6 +102,23 @@ class Accelerator:
             self.scaler.update()
         else:
             optimizer.step()
+
+    def clip_grad_norm_(self, parameters, max_norm: float) -> torch.Tensor:
+        """Clip the global gradient norm in place (accelerate's
+        ``clip_grad_norm_``); returns the pre-clip norm as an fp32[1] tensor
+        on the gradients' device, without a host sync on the GPU path. Call
+        at a sync boundary, before ``step``: pending DDP reductions are
+        finished and, under fp16, the gradients are unscaled first."""
+        from ..ops.grad_clip import clip_grad_norm_
+        params = [p for p in (
+            [parameters] if isinstance(parameters, torch.Tensor)
+            else parameters)]
+        model = getattr(self, "_model", None)
+        if isinstance(model, DistributedDataParallel):
+            model.finalize_backward()
+        if self.scaler is not None:
+            self.scaler.unscale_(_GradHolder(params))
+        return clip_grad_norm_(params, max_norm)
 
     def wait_for_everyone(self):
         if dist.is_initialized():

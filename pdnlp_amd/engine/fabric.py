@@ -98,6 +98,20 @@ class Fabric:
         else:
             optimizer.step()
 
+    def clip_gradients(self, model, optimizer, max_norm: float
+                       ) -> torch.Tensor:
+        """Clip the global gradient norm in place (Fabric's
+        ``clip_gradients(..., max_norm=)``); returns the pre-clip norm as an
+        fp32[1] tensor. Call before ``optimizer_step``: pending DDP
+        reductions are finished and, under "16-mixed", the gradients are
+        unscaled first (``optimizer_step`` does not unscale twice)."""
+        from ..ops.grad_clip import clip_grad_norm_
+        if isinstance(model, DistributedDataParallel):
+            model.finalize_backward()
+        if self.scaler is not None:
+            self.scaler.unscale_(optimizer)
+        return clip_grad_norm_(list(model.parameters()), max_norm)
+
     def print(self, *args, **kwargs):
         if (not dist.is_initialized()) or dist.get_rank() == 0:
             print(*args, **kwargs)

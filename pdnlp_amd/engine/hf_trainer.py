@@ -46,6 +46,9 @@ class TrainingArguments:
     gradient_accumulation_steps: int = 1
     dataloader_num_workers: int = 2
     unpad: bool = False   # the data_collator packs (Collate(unpad=True))
+    # global-norm gradient clipping, 0 = off. HF's own default is 1.0 (so
+    # the reference's transformers run clips); set 1.0 to reproduce it.
+    max_grad_norm: float = 0.0
 
 
 class HFStyleTrainer:
@@ -74,6 +77,7 @@ class HFStyleTrainer:
         eargs.grad_accum_steps = args.gradient_accumulation_steps
         eargs.seed = args.seed
         eargs.unpad = args.unpad
+        eargs.max_grad_norm = args.max_grad_norm
         eargs.output_dir = args.output_dir
         eargs.ckpt_path = os.path.join(args.output_dir, "best_model.pt")
         eargs.local_rank = init_distributed()

@@ -54,6 +54,15 @@ class Trainer:
         self._graph = None
         self._graph_warm = 0
         self._static = None
+        # global gradient norm of the last optimizer step as an fp32[1]
+        # DEVICE tensor (None while max_grad_norm is off); read on logged
+        # steps only, where the loss .item() syncs anyway
+        self.last_grad_norm = None
+        mgn = float(getattr(args, "max_grad_norm", 0.0) or 0.0)
+        if mgn > 0 and getattr(optimizer, "max_grad_norm", None) == 0.0:
+            # ZeRO / hooks clip inside step(): hand them the bound when the
+            # optimizer was built without build_training
+            optimizer.max_grad_norm = mgn
         # optional per-step hook: fn(trainer) called after every global step
         # (HFStyleTrainer uses it for checkpoint-N dirs)
         self.step_callback = None
@@ -116,22 +125,28 @@ class Trainer:
                 # fold replica grads into the primary (single-process DP)
                 self.model.sync_replica_grads()
 
-        if is_ddp and not accum_boundary:
-            with self.model.no_sync():
+        if not accum_boundary:
+            # micro-step: gradients only accumulate — no sync, no clip, no
+            # optimizer step until the boundary
+            if is_ddp:
+                with self.model.no_sync():
+                    _bw(loss)
+            else:
                 _bw(loss)
             return False
         _bw(loss)
         if is_ddp:
             self.model.finalize_backward()
-        if args.max_grad_norm and args.max_grad_norm > 0:
-            if self.scaler is not None:
-                self.scaler.unscale_(self.optimizer)
-            torch.nn.utils.clip_grad_norm_(
-                (p for p in self.model.parameters() if p.grad is not None),
-                args.max_grad_norm)
         with TraceRange("optimizer"):
             if self.scaler is not None and not is_zero:
-                self.scaler.step(self.optimizer)
+                if self._clips_here():
+                    # the clip must see unscaled gradients
+                    self.scaler.unscale_(self.optimizer)
+                coef = self._grad_coef()
+                if coef is not None:
+                    self.scaler.step(self.optimizer, grad_coef=coef)
+                else:
+                    self.scaler.step(self.optimizer)
                 self.scaler.update()
             elif self.scaler is not None and is_zero:
                 # grads were unscaled rank-LOCALLY (before reduce-scatter),
@@ -145,11 +160,52 @@ class Trainer:
                     self.optimizer.step()
                 self.scaler.update()
             else:
-                self.optimizer.step()
+                self._optimizer_step()
+        if not self._clips_here():
+            # ZeRO / hooks clip inside step(), after their own reduction
+            self.last_grad_norm = getattr(self.optimizer, "last_grad_norm",
+                                          None)
         if self.lr_scheduler is not None:
             self.lr_scheduler.step()
         self._zero_grad()
         return True
+
+    # ---- global-norm gradient clipping (ops/grad_clip.py) ----
+    def _clips_here(self) -> bool:
+        """True when the Trainer itself computes the clip coefficient.
+        Optimizers that reduce gradients inside ``step()`` (ZeRO, hooks)
+        carry ``max_grad_norm`` themselves and clip after the reduction."""
+        mgn = getattr(self.args, "max_grad_norm", 0.0)
+        return bool(mgn and mgn > 0
+                    and not hasattr(self.optimizer, "max_grad_norm"))
+
+    def _grad_coef(self):
+        """Device clip coefficient for the gradients as they stand (already
+        synchronized and unscaled), or None when there is nothing to pass
+        on. Fused optimizers take the coefficient into their kernels, so the
+        gradients are read once and never rewritten; any other optimizer
+        gets them scaled in place."""
+        if not self._clips_here():
+            return None
+        from ..ops.adamw import FusedAdamW, FusedSGD
+        from ..ops.grad_clip import grad_clip_coef, scale_
+        grads = [p.grad for p in self.model.parameters()
+                 if p.grad is not None]
+        if not grads:
+            return None
+        coef, norm = grad_clip_coef(grads, self.args.max_grad_norm)
+        self.last_grad_norm = norm
+        if isinstance(self.optimizer, (FusedAdamW, FusedSGD)):
+            return coef
+        scale_(grads, coef)
+        return None
+
+    def _optimizer_step(self):
+        coef = self._grad_coef()
+        if coef is not None:
+            self.optimizer.step(grad_coef=coef)
+        else:
+            self.optimizer.step()
 
     def _zero_grad(self):
         if isinstance(self.model, DistributedDataParallel):
@@ -198,7 +254,7 @@ class Trainer:
                     token_type_ids=self._static["token_type_ids"],
                     labels=self._static[self.label_key])
                 out.loss.backward()
-                self.optimizer.step()
+                self._optimizer_step()
         del out  # a live autograd graph from before the capture pins
         #          default/side-stream AccumulateGrad nodes and SEGFAULTS
         #          hipGraph instantiation (torch input_buffer stream check)
@@ -227,7 +283,9 @@ class Trainer:
                     non_blocking=True)
         reseed_dropout()
         self._graph.replay()
-        self.optimizer.step()   # grads overwritten in-place by the replay
+        # grads overwritten in-place by the replay; the clip runs eagerly
+        # between replay and step, like the optimizer itself
+        self._optimizer_step()
         if self.lr_scheduler is not None:
             self.lr_scheduler.step()
         return (self._static_loss, self._static_logits,
@@ -365,9 +423,12 @@ class Trainer:
                 f"【train】 epoch：{epoch}/{args.epochs} "
                 f"step：{self.global_step}/{total_step} "
                 f"loss：{printed_loss:.6f}")
+            extra = {}
+            if self.last_grad_norm is not None:
+                extra["grad_norm"] = float(self.last_grad_norm.item())
             self.metrics.write(
                 phase="train", epoch=epoch, step=self.global_step,
-                loss=printed_loss,
+                loss=printed_loss, **extra,
                 lr=self.optimizer.param_groups[0]["lr"]
                 if hasattr(self.optimizer, "param_groups") else args.learning_rate,
                 samples_per_sec=timer.samples_per_sec(),
@@ -519,6 +580,8 @@ def build_training(args, model=None, label_key: str = "label"):
             model, lr=args.learning_rate,
             betas=(args.adam_beta1, args.adam_beta2), eps=args.adam_eps,
             weight_decay=args.weight_decay, bucket_mb=args.bucket_cap_mb)
+        optimizer.max_grad_norm = float(getattr(args, "max_grad_norm", 0.0)
+                                        or 0.0)
         wrapped = model
     else:
         optimizer = build_optimizer(
@@ -536,6 +599,8 @@ def build_training(args, model=None, label_key: str = "label"):
                     "fp16": torch.float16}[args.grad_compression]
             optimizer = DistributedOptimizer(optimizer, compression=comp,
                                              fusion_mb=args.bucket_cap_mb)
+            optimizer.max_grad_norm = float(
+                getattr(args, "max_grad_norm", 0.0) or 0.0)
             broadcast_optimizer_state(optimizer.optimizer)
             wrapped = model
         elif args.strategy == "dp":

@@ -89,3 +89,9 @@ from .functional import (  # noqa: F401,E402
     dw_stream_join,
 )
 from .adamw import FusedAdamW, multi_tensor_adamw  # noqa: F401,E402
+from .grad_clip import (  # noqa: F401,E402
+    grad_sumsq,
+    grad_clip_coef,
+    clip_coef_from_sumsq,
+    clip_grad_norm_,
+)

@@ -26,11 +26,14 @@ def multi_tensor_adamw(params: List[torch.Tensor], grads: List[torch.Tensor],
                        lr: float, beta1: float, beta2: float, eps: float,
                        weight_decay: float, step: int,
                        grad_scale_inv: float = 1.0,
-                       found_inf: Optional[torch.Tensor] = None) -> None:
+                       found_inf: Optional[torch.Tensor] = None,
+                       grad_coef: Optional[torch.Tensor] = None) -> None:
     """Apply one AdamW step to a flat list of tensors (same group).
 
     ``found_inf``: optional fp32[1] device flag — the HIP kernel skips the
-    whole update when it is nonzero (AMP overflow, no host sync)."""
+    whole update when it is nonzero (AMP overflow, no host sync).
+    ``grad_coef``: optional fp32[1] device scalar multiplied into every
+    gradient as it is read (global-norm clip, ``ops.grad_clip_coef``)."""
     if not params:
         return
     bc1 = 1.0 - beta1 ** step
@@ -44,7 +47,7 @@ def multi_tensor_adamw(params: List[torch.Tensor], grads: List[torch.Tensor],
                 exp_avgs[i:i + CHUNK], exp_avg_sqs[i:i + CHUNK],
                 masters[i:i + CHUNK] if use_master else [],
                 lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale_inv,
-                finf)
+                finf, grad_coef)
         return
     if found_inf is not None and float(found_inf.item()) != 0.0:
         return  # torch fallback: synchronous skip
@@ -53,6 +56,8 @@ def multi_tensor_adamw(params: List[torch.Tensor], grads: List[torch.Tensor],
         for p, g, m, v, mw in zip(params, grads, exp_avgs, exp_avg_sqs, masters):
             w = mw if mw is not None else p
             gf = g.float() * grad_scale_inv
+            if grad_coef is not None:
+                gf = gf * grad_coef.to(gf.device)
             if weight_decay != 0.0:
                 w.mul_(1.0 - lr * weight_decay)
             m.mul_(beta1).add_(gf, alpha=1.0 - beta1)
@@ -84,7 +89,8 @@ class FusedAdamW(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale_inv: float = 1.0,
-             found_inf: Optional[torch.Tensor] = None):
+             found_inf: Optional[torch.Tensor] = None,
+             grad_coef: Optional[torch.Tensor] = None):
         from .functional import dw_stream_join
         dw_stream_join()   # no-op unless PDNLP_DW_STREAM=1
         loss = None
@@ -118,7 +124,8 @@ class FusedAdamW(torch.optim.Optimizer):
                 multi_tensor_adamw(params, grads, ms, vs, masters,
                                    group["lr"], b1, b2, group["eps"],
                                    group["weight_decay"], step, grad_scale_inv,
-                                   found_inf=found_inf)
+                                   found_inf=found_inf,
+                                   grad_coef=grad_coef)
         return loss
 
 
@@ -135,7 +142,10 @@ class FusedSGD(torch.optim.Optimizer):
         self.master_weights = master_weights
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None,
+             grad_coef: Optional[torch.Tensor] = None):
+        """``grad_coef``: optional fp32[1] device scalar multiplied into
+        every gradient as it is read (global-norm clip)."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -163,6 +173,8 @@ class FusedSGD(torch.optim.Optimizer):
                     masters.append(state["master"])
                     continue
                 g = p.grad.float()
+                if grad_coef is not None:
+                    g = g * grad_coef.to(g.device)
                 if group["weight_decay"]:
                     g = g.add(p.float(), alpha=group["weight_decay"])
                 if group["momentum"]:
@@ -180,7 +192,8 @@ class FusedSGD(torch.optim.Optimizer):
                         bufs[i:i + CHUNK],
                         masters[i:i + CHUNK] if use_master else [],
                         group["lr"], group["momentum"],
-                        group["weight_decay"], 1.0, torch.Tensor())
+                        group["weight_decay"], 1.0, torch.Tensor(),
+                        grad_coef)
         return loss
 
 

@@ -9,10 +9,13 @@
 // BERT tensors per step.
 //
 // Honors decoupled weight decay (per group), fp32 m/v, optional fp32 master
-// weights for bf16/fp16 params, and a fused grad-scale-inverse (AMP).
+// weights for bf16/fp16 params, a fused grad-scale-inverse (AMP), and an
+// optional device-side gradient-clip coefficient (grad_clip.hip).
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+
+#include <optional>
 
 #include "common.h"
 
@@ -42,10 +45,14 @@ template <typename T, bool MASTER>
 __global__ void adamw_kernel(AdamWMeta meta, float lr, float beta1,
                              float beta2, float eps, float wd, float bc1,
                              float bc2, float grad_scale_inv,
-                             const float* __restrict__ found_inf) {
+                             const float* __restrict__ found_inf,
+                             const float* __restrict__ grad_coef) {
   // AMP: skip the whole update on overflow, device-side (no host sync —
   // the GradScaler's per-step found_inf.item() stalls the launch pipeline)
   if (found_inf != nullptr && *found_inf != 0.f) return;
+  // global-norm clip: device coefficient (grad_clip.hip), read once per
+  // block and folded into the scale the gradients are multiplied by anyway
+  if (grad_coef != nullptr) grad_scale_inv *= *grad_coef;
   // find tensor for this block
   int t = 0;
   while (t + 1 < meta.ntensors && blockIdx.x >= meta.block_prefix[t + 1]) ++t;
@@ -132,8 +139,10 @@ struct SgdMeta {
 template <typename T, bool MASTER>
 __global__ void sgd_kernel(SgdMeta meta, float lr, float momentum, float wd,
                            float grad_scale_inv,
-                           const float* __restrict__ found_inf) {
+                           const float* __restrict__ found_inf,
+                           const float* __restrict__ grad_coef) {
   if (found_inf != nullptr && *found_inf != 0.f) return;
+  if (grad_coef != nullptr) grad_scale_inv *= *grad_coef;
   int t = 0;
   while (t + 1 < meta.ntensors && blockIdx.x >= meta.block_prefix[t + 1]) ++t;
   const long local_block = blockIdx.x - meta.block_prefix[t];
@@ -195,6 +204,15 @@ __global__ void unscale_kernel(UnscaleMeta meta, float* found_inf,
   if (__any(bad) && (threadIdx.x & (WAVE - 1)) == 0) *found_inf = 1.f;
 }
 
+// nullable device clip coefficient (fp32[1]); nullptr = no clipping
+const float* coef_ptr(const std::optional<torch::Tensor>& c) {
+  if (!c.has_value() || !c->defined() || c->numel() == 0) return nullptr;
+  TORCH_CHECK(c->is_cuda() && c->numel() == 1 &&
+                  c->scalar_type() == at::ScalarType::Float,
+              "grad_coef must be a 1-element fp32 device tensor");
+  return c->data_ptr<float>();
+}
+
 int blocks_of(long numel) {
   return (int)((numel + (long)BLOCK * ILP - 1) / ((long)BLOCK * ILP));
 }
@@ -208,11 +226,13 @@ void multi_tensor_adamw(std::vector<torch::Tensor> params,
                         std::vector<torch::Tensor> masters, double lr,
                         double beta1, double beta2, double eps,
                         double weight_decay, double bc1, double bc2,
-                        double grad_scale_inv, torch::Tensor found_inf) {
+                        double grad_scale_inv, torch::Tensor found_inf,
+                        std::optional<torch::Tensor> grad_coef) {
   TORCH_CHECK(!params.empty());
   const float* finf = (found_inf.defined() && found_inf.numel() > 0)
                           ? found_inf.data_ptr<float>()
                           : nullptr;
+  const float* gcoef = coef_ptr(grad_coef);
   const bool master = !masters.empty();
   auto stream = at::hip::getCurrentHIPStream();
   const auto dtype = params[0].scalar_type();
@@ -243,13 +263,13 @@ void multi_tensor_adamw(std::vector<torch::Tensor> params,
                            dim3(BLOCK), 0, stream, meta, (float)lr,
                            (float)beta1, (float)beta2, (float)eps,
                            (float)weight_decay, (float)bc1, (float)bc2,
-                           (float)grad_scale_inv, finf);
+                           (float)grad_scale_inv, finf, gcoef);
       } else {
         hipLaunchKernelGGL((adamw_kernel<scalar_t, false>), dim3(blocks),
                            dim3(BLOCK), 0, stream, meta, (float)lr,
                            (float)beta1, (float)beta2, (float)eps,
                            (float)weight_decay, (float)bc1, (float)bc2,
-                           (float)grad_scale_inv, finf);
+                           (float)grad_scale_inv, finf, gcoef);
       }
     });
   }
@@ -260,11 +280,13 @@ void multi_tensor_sgd(std::vector<torch::Tensor> params,
                       std::vector<torch::Tensor> bufs,
                       std::vector<torch::Tensor> masters, double lr,
                       double momentum, double weight_decay,
-                      double grad_scale_inv, torch::Tensor found_inf) {
+                      double grad_scale_inv, torch::Tensor found_inf,
+                        std::optional<torch::Tensor> grad_coef) {
   TORCH_CHECK(!params.empty());
   const float* finf = (found_inf.defined() && found_inf.numel() > 0)
                           ? found_inf.data_ptr<float>()
                           : nullptr;
+  const float* gcoef = coef_ptr(grad_coef);
   const bool master = !masters.empty();
   auto stream = at::hip::getCurrentHIPStream();
   const auto dtype = params[0].scalar_type();
@@ -293,12 +315,12 @@ void multi_tensor_sgd(std::vector<torch::Tensor> params,
         hipLaunchKernelGGL((sgd_kernel<scalar_t, true>), dim3(blocks),
                            dim3(BLOCK), 0, stream, meta, (float)lr,
                            (float)momentum, (float)weight_decay,
-                           (float)grad_scale_inv, finf);
+                           (float)grad_scale_inv, finf, gcoef);
       } else {
         hipLaunchKernelGGL((sgd_kernel<scalar_t, false>), dim3(blocks),
                            dim3(BLOCK), 0, stream, meta, (float)lr,
                            (float)momentum, (float)weight_decay,
-                           (float)grad_scale_inv, finf);
+                           (float)grad_scale_inv, finf, gcoef);
       }
     });
   }

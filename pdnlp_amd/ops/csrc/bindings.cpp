@@ -2,6 +2,7 @@
 
 #include <torch/extension.h>
 
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -43,7 +44,8 @@ void multi_tensor_sgd(std::vector<torch::Tensor> params,
                       std::vector<torch::Tensor> bufs,
                       std::vector<torch::Tensor> masters, double lr,
                       double momentum, double weight_decay,
-                      double grad_scale_inv, torch::Tensor found_inf);
+                      double grad_scale_inv, torch::Tensor found_inf,
+                        std::optional<torch::Tensor> grad_coef);
 torch::Tensor tanh_bwd(torch::Tensor dy, torch::Tensor pre);
 std::vector<torch::Tensor> bias_dropout_residual_ln_fwd(
     torch::Tensor y, torch::Tensor bias, torch::Tensor res, torch::Tensor lnw,
@@ -66,9 +68,18 @@ void multi_tensor_adamw(std::vector<torch::Tensor> params,
                         std::vector<torch::Tensor> masters, double lr,
                         double beta1, double beta2, double eps,
                         double weight_decay, double bc1, double bc2,
-                        double grad_scale_inv, torch::Tensor found_inf);
+                        double grad_scale_inv, torch::Tensor found_inf,
+                        std::optional<torch::Tensor> grad_coef);
 void multi_tensor_unscale(std::vector<torch::Tensor> grads,
                           torch::Tensor found_inf, double inv_scale);
+void multi_tensor_sumsq(std::vector<torch::Tensor> tensors, torch::Tensor out,
+                        bool accumulate, double max_norm,
+                        std::optional<torch::Tensor> coef_out,
+                        std::optional<torch::Tensor> norm_out);
+void clip_coef_from_sumsq(torch::Tensor sumsq, double max_norm,
+                          torch::Tensor coef_out, torch::Tensor norm_out);
+void multi_tensor_scale_(std::vector<torch::Tensor> tensors,
+                         torch::Tensor coef);
 std::vector<torch::Tensor> gemm_nt_fwd(torch::Tensor A, torch::Tensor W,
                                        torch::Tensor bias, std::string act);
 std::vector<torch::Tensor> flash_attn_qkv_fwd(torch::Tensor qkv,
@@ -111,7 +122,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_linear_bwd", &skinny_linear_bwd);
   m.def("dropout_fwd", &dropout_fwd);
   m.def("dropout_bwd", &dropout_bwd);
-  m.def("multi_tensor_sgd", &multi_tensor_sgd);
+  // grad_coef: optional fp32[1] device clip coefficient (grad_clip.hip);
+  // trailing and defaulted, the positional 9/14-argument forms still work
+  m.def("multi_tensor_sgd", &multi_tensor_sgd, py::arg("params"),
+        py::arg("grads"), py::arg("bufs"), py::arg("masters"), py::arg("lr"),
+        py::arg("momentum"), py::arg("weight_decay"),
+        py::arg("grad_scale_inv"), py::arg("found_inf"),
+        py::arg("grad_coef") = py::none());
   m.def("tanh_bwd", &tanh_bwd);
   m.def("bias_dropout_residual_ln_fwd", &bias_dropout_residual_ln_fwd);
   m.def("bias_dropout_residual_ln_bwd", &bias_dropout_residual_ln_bwd);
@@ -119,7 +136,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         &bias_dropout_residual_ln_bwd_nodb);
   m.def("cross_entropy_fwd", &cross_entropy_fwd);
   m.def("cross_entropy_bwd", &cross_entropy_bwd);
-  m.def("multi_tensor_adamw", &multi_tensor_adamw);
+  m.def("multi_tensor_adamw", &multi_tensor_adamw, py::arg("params"),
+        py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"),
+        py::arg("masters"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("eps"), py::arg("weight_decay"), py::arg("bc1"),
+        py::arg("bc2"), py::arg("grad_scale_inv"), py::arg("found_inf"),
+        py::arg("grad_coef") = py::none());
+  m.def("multi_tensor_sumsq", &multi_tensor_sumsq, py::arg("tensors"),
+        py::arg("out"), py::arg("accumulate"), py::arg("max_norm") = 0.0,
+        py::arg("coef_out") = py::none(), py::arg("norm_out") = py::none());
+  m.def("clip_coef_from_sumsq", &clip_coef_from_sumsq);
+  m.def("multi_tensor_scale_", &multi_tensor_scale_);
   m.def("multi_tensor_unscale", &multi_tensor_unscale);
   m.def("gemm_nt_fwd", &gemm_nt_fwd);
   m.def("flash_attn_qkv_fwd", &flash_attn_qkv_fwd);

@@ -53,6 +53,11 @@ class DistributedOptimizer:
         self.average = average
         self.param_groups = optimizer.param_groups
         self.state = optimizer.state
+        # global-norm clip of the AVERAGED gradient, applied inside step()
+        # after the all-reduce (0 = off); last_grad_norm is the fp32[1]
+        # norm tensor of the last clipped step
+        self.max_grad_norm = 0.0
+        self.last_grad_norm: Optional[torch.Tensor] = None
 
     def _params_with_grads(self):
         for g in self.optimizer.param_groups:
@@ -89,6 +94,15 @@ class DistributedOptimizer:
 
     def step(self, closure=None):
         self._allreduce_grads()
+        if self.max_grad_norm and self.max_grad_norm > 0:
+            from ..ops.adamw import FusedAdamW, FusedSGD
+            from ..ops.grad_clip import grad_clip_coef, scale_
+            grads = [p.grad for p in self._params_with_grads()]
+            coef, norm = grad_clip_coef(grads, self.max_grad_norm)
+            self.last_grad_norm = norm
+            if isinstance(self.optimizer, (FusedAdamW, FusedSGD)):
+                return self.optimizer.step(closure, grad_coef=coef)
+            scale_(grads, coef)
         return self.optimizer.step(closure)
 
     def zero_grad(self, set_to_none: bool = True):

@@ -62,6 +62,11 @@ class ZeroRedundancyOptimizer:
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.step_count = 0
         self.bucket_bytes = int(bucket_mb * 1024 * 1024)
+        # global-norm clip of the AVERAGED gradient, applied inside step()
+        # after the reduce-scatter (0 = off); last_grad_norm is the fp32[1]
+        # device norm of the last clipped step
+        self.max_grad_norm = 0.0
+        self.last_grad_norm: Optional[torch.Tensor] = None
 
         if dist.is_initialized():
             for t in model.state_dict().values():
@@ -125,6 +130,9 @@ class ZeroRedundancyOptimizer:
         from ..ops.functional import dw_stream_join
         dw_stream_join()   # no-op unless PDNLP_DW_STREAM=1
         self.step_count += 1
+        if self.max_grad_norm and self.max_grad_norm > 0:
+            self._clipped_step(grad_scale_inv, found_inf)
+            return
         for g, pg in zip(self.groups, self.param_groups):
             lo = self.rank * g.shard_size
             shard_grad = self._reduce_scatter(g)
@@ -134,6 +142,35 @@ class ZeroRedundancyOptimizer:
                 pg["lr"], self.betas[0], self.betas[1], self.eps,
                 g.weight_decay, self.step_count, grad_scale_inv,
                 found_inf=found_inf)
+            self._all_gather(g)
+
+    def _clipped_step(self, grad_scale_inv, found_inf):
+        """step() with global-norm clipping: every group is reduce-scattered
+        first, the sum of squares of the local (averaged) shards is
+        all-reduced — shards are disjoint and their padding is zero, so the
+        sum is the squared norm of the full averaged gradient — and the
+        resulting device coefficient rides into the sharded AdamW kernels.
+        Nothing here synchronizes the host."""
+        from ..ops.grad_clip import grad_clip_coef
+        shards = [self._reduce_scatter(g) for g in self.groups]
+
+        def _sum_over_ranks(sumsq):
+            if grad_scale_inv != 1.0:
+                sumsq.mul_(grad_scale_inv * grad_scale_inv)
+            if dist.is_initialized() and self.world > 1:
+                dist.all_reduce(sumsq, op=dist.ReduceOp.SUM, group=self.group)
+
+        coef, norm = grad_clip_coef(shards, self.max_grad_norm,
+                                    extra_sumsq_reduce=_sum_over_ranks)
+        self.last_grad_norm = norm
+        for g, pg, shard_grad in zip(self.groups, self.param_groups, shards):
+            lo = self.rank * g.shard_size
+            multi_tensor_adamw(
+                [g.param_flat[lo:lo + g.shard_size]], [shard_grad],
+                [g.m_shard], [g.v_shard], [g.master_shard],
+                pg["lr"], self.betas[0], self.betas[1], self.eps,
+                g.weight_decay, self.step_count, grad_scale_inv,
+                found_inf=found_inf, grad_coef=coef)
             self._all_gather(g)
 
     def _reduce_scatter(self, g: _FlatGroup) -> torch.Tensor:
