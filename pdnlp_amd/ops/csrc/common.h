@@ -52,6 +52,24 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// LayerNorm row statistics from the one-pass sums of d = x - shift, shift
+// being the row's first element: sum = SUM d, sumsq = SUM d*d over H columns.
+// var = E[d^2] - E[d]^2 cancels only by (mean - shift)^2 / var, a few units
+// for a sample of the row, where the unshifted E[x^2] - mean^2 loses
+// mean^2 / var of fp32's 2^-24 (a row of mean 100, std 1: 1e-3 in rstd; a
+// constant row: var + eps <= 0 and a NaN). The clamp keeps the rounding of
+// an exactly flat row from going negative. md = mean - shift is returned
+// too: x - shift - md normalises without the rounding of mean to fp32,
+// which at |mean| = 100 is 4e-6 of a standard deviation.
+__device__ __forceinline__ void shifted_stats(float sum, float sumsq,
+                                              float shift, int H, float eps,
+                                              float& md, float& mean,
+                                              float& rstd) {
+  md = sum / H;
+  mean = shift + md;
+  rstd = rsqrtf(fmaxf(sumsq / H - md * md, 0.f) + eps);
+}
+
 // block reduction over NW waves (NW <= 16), via LDS; returns on all threads
 template <int NW>
 __device__ __forceinline__ float block_sum(float v, float* lds_scratch) {

@@ -34,23 +34,25 @@ __global__ void emb_ln_fwd_kernel(
   const T* tr = type_ + (long)type_ids[row] * H;
   T* yr = y + (long)row * H;
 
+  // one-pass statistics of x - shift (see shifted_stats in common.h)
+  const float shift = to_f32<T>(wr[0]) + to_f32<T>(pr[0]) + to_f32<T>(tr[0]);
   float sum = 0.f, sumsq = 0.f;
   for (int c = lane; c < H; c += WAVE) {
-    const float v = to_f32<T>(wr[c]) + to_f32<T>(pr[c]) + to_f32<T>(tr[c]);
+    const float v =
+        to_f32<T>(wr[c]) + to_f32<T>(pr[c]) + to_f32<T>(tr[c]) - shift;
     sum += v;
     sumsq += v * v;
   }
-  sum = wave_sum(sum);
-  sumsq = wave_sum(sumsq);
-  const float mean = sum / H;
-  const float rstd = rsqrtf(sumsq / H - mean * mean + eps);
+  float md, mean, rstd;  // md = mean - shift
+  shifted_stats(wave_sum(sum), wave_sum(sumsq), shift, H, eps, md, mean, rstd);
   if (lane == 0) {
     mean_out[row] = mean;
     rstd_out[row] = rstd;
   }
   for (int c = lane; c < H; c += WAVE) {
     const float v = to_f32<T>(wr[c]) + to_f32<T>(pr[c]) + to_f32<T>(tr[c]);
-    yr[c] = from_f32<T>((v - mean) * rstd * to_f32<T>(w[c]) + to_f32<T>(b[c]));
+    yr[c] = from_f32<T>((v - shift - md) * rstd * to_f32<T>(w[c]) +
+                        to_f32<T>(b[c]));
   }
 }
 

@@ -65,6 +65,15 @@ void bdrl_fwd_kernel(const T* __restrict__ y, const T* __restrict__ bias,
   T* outr = out + row * H;
   const float inv_keep = 1.f / (1.f - p);
 
+  // one-pass statistics of xsum - shift (see shifted_stats in common.h);
+  // every lane derives the row's first xsum element the way the loop does
+  float shift = to_f32<T>(yr[0]) + to_f32<T>(bias[0]);
+  if (DROP) {
+    const unsigned int r = hash_rng(seed, row * (unsigned long long)H);
+    shift = (r * 2.3283064365386963e-10f) >= p ? shift * inv_keep : 0.f;
+  }
+  shift = to_f32<T>(from_f32<T>(shift + to_f32<T>(rr[0])));
+
   float sum = 0.f, sumsq = 0.f;
   for (int c = lane * 4; c < H; c += WAVE * 4) {
     const v4_t<T> yv = ld4(yr + c), bv = ld4(bias + c), rv = ld4(rr + c);
@@ -83,17 +92,15 @@ void bdrl_fwd_kernel(const T* __restrict__ y, const T* __restrict__ bias,
       h += elem<T>(rv, j);
       set_elem<T>(xv, j, h);
       // stats from the rounded value so they match the saved xsum exactly
-      const float hs = elem<T>(xv, j);
+      const float hs = elem<T>(xv, j) - shift;
       sum += hs;
       sumsq += hs * hs;
     }
     st4(xr + c, xv);
     if (DROP) *reinterpret_cast<uchar4*>(mask_out + row * H + c) = mv;
   }
-  sum = wave_sum(sum);
-  sumsq = wave_sum(sumsq);
-  const float mean = sum / H;
-  const float rstd = rsqrtf(sumsq / H - mean * mean + eps);
+  float md, mean, rstd;  // md = mean - shift
+  shifted_stats(wave_sum(sum), wave_sum(sumsq), shift, H, eps, md, mean, rstd);
   if (lane == 0) {
     mean_out[row] = mean;
     rstd_out[row] = rstd;
@@ -103,7 +110,7 @@ void bdrl_fwd_kernel(const T* __restrict__ y, const T* __restrict__ bias,
     v4_t<T> ov;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float xh = (elem<T>(xv, j) - mean) * rstd;
+      const float xh = (elem<T>(xv, j) - shift - md) * rstd;
       set_elem<T>(ov, j, xh * elem<T>(wv, j) + elem<T>(bv, j));
     }
     st4(outr + c, ov);

@@ -46,7 +46,7 @@ __global__ void bias_gelu_fwd_kernel(const T* __restrict__ x,
       *reinterpret_cast<short4*>(y + i) = o0;
       *reinterpret_cast<short4*>(y + i + 4) = o1;
     } else {
-      for (long k = i; k < total; ++k) {
+      for (long k = i; k < min(i + 8, total); ++k) {
         y[k] = from_f32<T>(gelu_f(to_f32<T>(x[k]) + to_f32<T>(b[k % N])));
       }
     }

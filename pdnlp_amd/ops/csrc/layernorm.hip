@@ -28,6 +28,8 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ w,
   const T* xr = x + (long)row * H;
   T* yr = y + (long)row * H;
 
+  // one-pass statistics of x - shift (see shifted_stats in common.h)
+  const float shift = to_f32<T>(xr[0]);
   float sum = 0.f, sumsq = 0.f;
   if (VEC == 4) {
     for (int base = lane * 4; base < H; base += WAVE * 4) {
@@ -35,23 +37,20 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ w,
       const T* px = reinterpret_cast<const T*>(&raw);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        float v = to_f32<T>(px[j]);
+        float v = to_f32<T>(px[j]) - shift;
         sum += v;
         sumsq += v * v;
       }
     }
   } else {
     for (int c = lane; c < H; c += WAVE) {
-      float v = to_f32<T>(xr[c]);
+      float v = to_f32<T>(xr[c]) - shift;
       sum += v;
       sumsq += v * v;
     }
   }
-  sum = wave_sum(sum);
-  sumsq = wave_sum(sumsq);
-  const float mean = sum / H;
-  const float var = sumsq / H - mean * mean;
-  const float rstd = rsqrtf(var + eps);
+  float md, mean, rstd;  // md = mean - shift
+  shifted_stats(wave_sum(sum), wave_sum(sumsq), shift, H, eps, md, mean, rstd);
   if (lane == 0) {
     mean_out[row] = mean;
     rstd_out[row] = rstd;
@@ -68,14 +67,14 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ w,
       T* py = reinterpret_cast<T*>(&ry);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        float v = (to_f32<T>(px[j]) - mean) * rstd;
+        float v = (to_f32<T>(px[j]) - shift - md) * rstd;
         py[j] = from_f32<T>(v * to_f32<T>(pw[j]) + to_f32<T>(pb[j]));
       }
       *reinterpret_cast<short4*>(yr + base) = ry;
     }
   } else {
     for (int c = lane; c < H; c += WAVE) {
-      float v = (to_f32<T>(xr[c]) - mean) * rstd;
+      float v = (to_f32<T>(xr[c]) - shift - md) * rstd;
       yr[c] = from_f32<T>(v * to_f32<T>(w[c]) + to_f32<T>(b[c]));
     }
   }

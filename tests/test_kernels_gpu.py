@@ -427,6 +427,22 @@ def test_flash_attn_dropout_bwd_matches_masked_ref():
     # rate sanity: ~p of entries dropped
     drop_rate = 1.0 - keep.float().mean().item()
     assert abs(drop_rate - p) < 0.05
+    assert (p0 != 0).all()   # else a dropped entry could not be told apart
+
+    # forward and backward on the real V against the fp32 reference under
+    # that mask (B = nh = 1: the [S, S] probe output is the mask of the
+    # only head)
+    o, lse = e.flash_attn_qkv_fwd(qkv, torch.Tensor(), nh, scale, p, seed, 5)
+    dout = torch.randn(B, S, H, device=DEV, dtype=torch.bfloat16)
+    dqkv = e.flash_attn_qkv_bwd(dout, qkv, o, lse, torch.Tensor(), nh, scale,
+                                p, seed, 5)
+    qr = qkv.float().detach().requires_grad_()
+    q, k, v = qr.split(H, dim=-1)
+    pr = F.softmax(torch.matmul(q, k.transpose(-1, -2)) * scale, dim=-1)
+    ref = torch.matmul(pr * keep.float() / (1.0 - p), v)
+    torch.testing.assert_close(o.float(), ref.detach(), rtol=3e-2, atol=3e-2)
+    ref.backward(dout.float())
+    torch.testing.assert_close(dqkv.float(), qr.grad, rtol=5e-2, atol=5e-2)
 
 
 def test_col_sum():

@@ -188,9 +188,9 @@ def _recover_probs(e, qkv, cu, cu_t, mx, p, seed, salt):
     return out
 
 
-def test_varlen_dropout():
+def _check_varlen_dropout(lens):
     e = ext()
-    lens, p = [65, 17], 0.1
+    p = 0.1
     cu = _cu(lens)
     total = cu[-1]
     T = _round64(total)
@@ -228,6 +228,16 @@ def test_varlen_dropout():
     ref.backward(dout.float())
     assert torch.isfinite(dqkv).all() and (dqkv[total:] == 0).all()
     torch.testing.assert_close(dqkv.float(), q32.grad, **BWD_TOL)
+
+
+def test_varlen_dropout():
+    _check_varlen_dropout([65, 17])
+
+
+def test_varlen_dropout_streamed():
+    """max_seqlen > 128: the kernels stream K/V tiles instead of preloading
+    them; 129 ends one key into its third tile."""
+    _check_varlen_dropout([129, 70])
 
 
 # ------------------------------------------------------------------- model
