@@ -754,43 +754,94 @@ static void check_fa_args(const torch::Tensor& qkv, const torch::Tensor& mask,
   }
 }
 
-// launch macros live at file scope (a #define cannot appear inside a macro
-// argument — DISPATCH_FLOAT_TYPES takes the body as one). The call site
-// provides: S (padded sequence length; packed row count T under VARLEN),
-// seq_max (longest sequence: picks PRELOAD), has_mask/mask, cu_ptr.
-#define FA_FWD_L(PL)                                                           \
-  hipLaunchKernelGGL((fa_fwd_kernel<scalar_t, V8, HM, DR, PL, VL>), grid,      \
-                     dim3(NTHREADS), 0, stream,                                \
-                     (const scalar_t*)qkv.data_ptr(),                          \
-                     has_mask ? (const scalar_t*)mask.data_ptr() : nullptr,    \
-                     (scalar_t*)o.data_ptr(), (float*)lse.data_ptr(),          \
-                     seed_ptr, (unsigned long long)salt, (float)scale,         \
-                     (float)p, (int)nh, (int)S, cu_ptr)
-#define FA_FWD(HMV, DRV, VLV)                                                  \
-  do {                                                                         \
-    constexpr bool HM = HMV, DR = DRV, VL = VLV;                               \
-    if (seq_max <= 128) FA_FWD_L(true);                                        \
-    else FA_FWD_L(false);                                                      \
-  } while (0)
+// Launch helpers shared by the padded and the packed (VARLEN) entry points.
+// S is the padded sequence length, or the packed row count T under VARLEN;
+// seq_max the longest sequence (picks PRELOAD and the grid); cu_seqlens is
+// nullptr for padded batches. VARLEN instantiates HAS_MASK = false only.
+struct FaLaunch {
+  dim3 grid;
+  hipStream_t stream;
+  const unsigned long long* seed;  // nullptr without dropout
+  bool has_mask, drop, preload;
+};
 
-#define FA_BWD_L(KERN, PL)                                                     \
-  hipLaunchKernelGGL((KERN<scalar_t, V8, HM, DR, PL, VL>), grid,               \
-                     dim3(NTHREADS), 0, stream,                                \
-                     (const scalar_t*)dout.data_ptr(),                         \
-                     (const scalar_t*)qkv.data_ptr(),                          \
-                     (const scalar_t*)o.data_ptr(),                            \
-                     (const float*)lse.data_ptr(),                             \
-                     (float*)dvec.data_ptr(),                                  \
-                     has_mask ? (const scalar_t*)mask.data_ptr() : nullptr,    \
-                     (scalar_t*)dqkv.data_ptr(), seed_ptr,                     \
-                     (unsigned long long)salt, (float)scale, (float)p,         \
-                     (int)nh, (int)S, cu_ptr)
-#define FA_BWD(KERN, HMV, DRV, VLV)                                            \
-  do {                                                                         \
-    constexpr bool HM = HMV, DR = DRV, VL = VLV;                               \
-    if (seq_max <= 128) FA_BWD_L(KERN, true);                                  \
-    else FA_BWD_L(KERN, false);                                                \
-  } while (0)
+static FaLaunch fa_launch_setup(const torch::Tensor& mask, long seq_max,
+                                long batch_heads, double p,
+                                const torch::Tensor& seed_buf) {
+  FaLaunch L;
+  L.grid = dim3((seq_max + 63) / 64, batch_heads);
+  L.stream = at::hip::getCurrentHIPStream();
+  L.has_mask = mask.defined() && mask.numel() > 0;
+  L.drop = p > 0.0;
+  L.preload = seq_max <= 128;
+  TORCH_CHECK(!L.drop || (seed_buf.defined() && seed_buf.is_cuda() &&
+                          seed_buf.scalar_type() == torch::kLong),
+              "flash_attn: dropout needs a cuda int64 seed buffer");
+  L.seed = L.drop ? (const unsigned long long*)seed_buf.data_ptr() : nullptr;
+  return L;
+}
+
+// runs the lambda with scalar_t, V8, HAS_MASK, DROP and PRELOAD bound
+#define FA_DISPATCH(DTYPE, L, VARLEN, ...)                                     \
+  DISPATCH_FLOAT_TYPES(DTYPE, "flash_attn", [&] {                              \
+    if constexpr (!std::is_same<scalar_t, float>::value) {                     \
+      using V8 = std::conditional_t<                                           \
+          std::is_same<scalar_t, __hip_bfloat16>::value, bf16x8, f16x8>;       \
+      DISPATCH_BOOL(L.has_mask, HM_, [&] {                                     \
+        constexpr bool HAS_MASK = !VARLEN && HM_;                              \
+        DISPATCH_BOOL(L.drop, DROP, [&] {                                      \
+          DISPATCH_BOOL(L.preload, PRELOAD, [&] { __VA_ARGS__(); });           \
+        });                                                                    \
+      });                                                                      \
+    } else {                                                                   \
+      TORCH_CHECK(false, "flash_attn: fp32 not supported");                    \
+    }                                                                          \
+  })
+
+template <bool VARLEN>
+static void fa_fwd_launch(const torch::Tensor& qkv, const torch::Tensor& mask,
+                          torch::Tensor& o, torch::Tensor& lse,
+                          const int* cu_seqlens, long seq_max, long batch,
+                          long S, long nh, double scale, double p,
+                          const torch::Tensor& seed_buf, long salt) {
+  const FaLaunch L = fa_launch_setup(mask, seq_max, batch * nh, p, seed_buf);
+  FA_DISPATCH(qkv.scalar_type(), L, VARLEN, [&] {
+    hipLaunchKernelGGL(
+        (fa_fwd_kernel<scalar_t, V8, HAS_MASK, DROP, PRELOAD, VARLEN>), L.grid,
+        dim3(NTHREADS), 0, L.stream, (const scalar_t*)qkv.data_ptr(),
+        HAS_MASK ? (const scalar_t*)mask.data_ptr() : nullptr,
+        (scalar_t*)o.data_ptr(), (float*)lse.data_ptr(), L.seed,
+        (unsigned long long)salt, (float)scale, (float)p, (int)nh, (int)S,
+        cu_seqlens);
+  });
+}
+
+// Dvec = rowsum(dO*O) is computed inside the dQ pass (it already stages dO;
+// O goes through the dS buffer) and consumed by dK/dV
+template <bool VARLEN>
+static void fa_bwd_launch(const torch::Tensor& dout, const torch::Tensor& qkv,
+                          const torch::Tensor& o, const torch::Tensor& lse,
+                          const torch::Tensor& mask, torch::Tensor& dvec,
+                          torch::Tensor& dqkv, const int* cu_seqlens,
+                          long seq_max, long batch, long S, long nh,
+                          double scale, double p,
+                          const torch::Tensor& seed_buf, long salt) {
+  const FaLaunch L = fa_launch_setup(mask, seq_max, batch * nh, p, seed_buf);
+  FA_DISPATCH(qkv.scalar_type(), L, VARLEN, [&] {
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(
+          kernel, L.grid, dim3(NTHREADS), 0, L.stream,
+          (const scalar_t*)dout.data_ptr(), (const scalar_t*)qkv.data_ptr(),
+          (const scalar_t*)o.data_ptr(), (const float*)lse.data_ptr(),
+          (float*)dvec.data_ptr(),
+          HAS_MASK ? (const scalar_t*)mask.data_ptr() : nullptr,
+          (scalar_t*)dqkv.data_ptr(), L.seed, (unsigned long long)salt,
+          (float)scale, (float)p, (int)nh, (int)S, cu_seqlens);
+    };
+    launch(fa_bwd_dq_kernel<scalar_t, V8, HAS_MASK, DROP, PRELOAD, VARLEN>);
+    launch(fa_bwd_dkv_kernel<scalar_t, V8, HAS_MASK, DROP, PRELOAD, VARLEN>);
+  });
+}
 
 std::vector<torch::Tensor> flash_attn_qkv_fwd(torch::Tensor qkv,
                                               torch::Tensor mask, long nh,
@@ -799,32 +850,10 @@ std::vector<torch::Tensor> flash_attn_qkv_fwd(torch::Tensor qkv,
                                               long salt) {
   check_fa_args(qkv, mask, nh);
   const long B = qkv.size(0), S = qkv.size(1), H = (long)nh * 64;
-  const long seq_max = S;
-  const int* cu_ptr = nullptr;
-  const bool has_mask = mask.defined() && mask.numel() > 0;
-  const bool drop = p > 0.0;
-  TORCH_CHECK(!drop || (seed_buf.defined() && seed_buf.is_cuda() &&
-                        seed_buf.scalar_type() == torch::kLong),
-              "flash_attn: dropout needs a cuda int64 seed buffer");
   auto o = torch::empty({B, S, H}, qkv.options());
   auto lse = torch::empty({B * nh, S}, qkv.options().dtype(torch::kFloat));
-  dim3 grid(S / 64, B * nh);
-  auto stream = at::hip::getCurrentHIPStream();
-  const auto* seed_ptr =
-      drop ? (const unsigned long long*)seed_buf.data_ptr() : nullptr;
-
-  DISPATCH_FLOAT_TYPES(qkv.scalar_type(), "flash_attn_qkv_fwd", [&] {
-    if constexpr (!std::is_same<scalar_t, float>::value) {
-      using V8 = std::conditional_t<
-          std::is_same<scalar_t, __hip_bfloat16>::value, bf16x8, f16x8>;
-      if (has_mask && drop) FA_FWD(true, true, false);
-      else if (has_mask) FA_FWD(true, false, false);
-      else if (drop) FA_FWD(false, true, false);
-      else FA_FWD(false, false, false);
-    } else {
-      TORCH_CHECK(false, "flash_attn: fp32 not supported");
-    }
-  });
+  fa_fwd_launch<false>(qkv, mask, o, lse, nullptr, S, B, S, nh, scale, p,
+                       seed_buf, salt);
   return {o, lse};
 }
 
@@ -834,40 +863,10 @@ torch::Tensor flash_attn_qkv_bwd(torch::Tensor dout, torch::Tensor qkv,
                                  double p, torch::Tensor seed_buf, long salt) {
   check_fa_args(qkv, mask, nh);
   const long B = qkv.size(0), S = qkv.size(1);
-  const long seq_max = S;
-  const int* cu_ptr = nullptr;
-  const bool has_mask = mask.defined() && mask.numel() > 0;
-  const bool drop = p > 0.0;
   auto dqkv = torch::empty_like(qkv);
   auto dvec = torch::empty({B * nh, S}, qkv.options().dtype(torch::kFloat));
-  auto stream = at::hip::getCurrentHIPStream();
-  const auto* seed_ptr =
-      drop ? (const unsigned long long*)seed_buf.data_ptr() : nullptr;
-
-  DISPATCH_FLOAT_TYPES(qkv.scalar_type(), "flash_attn_qkv_bwd", [&] {
-    if constexpr (!std::is_same<scalar_t, float>::value) {
-      using V8 = std::conditional_t<
-          std::is_same<scalar_t, __hip_bfloat16>::value, bf16x8, f16x8>;
-      // Dvec = rowsum(dO*O) is computed inside the dQ pass (it already
-      // stages dO; O goes through the dS buffer) and consumed by dK/dV
-      dim3 grid(S / 64, B * nh);
-      if (has_mask && drop) {
-        FA_BWD(fa_bwd_dq_kernel, true, true, false);
-        FA_BWD(fa_bwd_dkv_kernel, true, true, false);
-      } else if (has_mask) {
-        FA_BWD(fa_bwd_dq_kernel, true, false, false);
-        FA_BWD(fa_bwd_dkv_kernel, true, false, false);
-      } else if (drop) {
-        FA_BWD(fa_bwd_dq_kernel, false, true, false);
-        FA_BWD(fa_bwd_dkv_kernel, false, true, false);
-      } else {
-        FA_BWD(fa_bwd_dq_kernel, false, false, false);
-        FA_BWD(fa_bwd_dkv_kernel, false, false, false);
-      }
-    } else {
-      TORCH_CHECK(false, "flash_attn: fp32 not supported");
-    }
-  });
+  fa_bwd_launch<false>(dout, qkv, o, lse, mask, dvec, dqkv, nullptr, S, B, S,
+                       nh, scale, p, seed_buf, salt);
   return dqkv;
 }
 
@@ -913,33 +912,13 @@ std::vector<torch::Tensor> flash_attn_varlen_fwd(torch::Tensor qkv,
                                                  long salt) {
   check_fa_varlen_args(qkv, cu_seqlens, max_seqlen, nh);
   const long S = qkv.size(0), B = cu_seqlens.numel() - 1, H = (long)nh * 64;
-  const long seq_max = max_seqlen;
-  const int* cu_ptr = (const int*)cu_seqlens.data_ptr();
-  const bool has_mask = false;
-  torch::Tensor mask;
-  const bool drop = p > 0.0;
-  TORCH_CHECK(!drop || (seed_buf.defined() && seed_buf.is_cuda() &&
-                        seed_buf.scalar_type() == torch::kLong),
-              "flash_attn_varlen: dropout needs a cuda int64 seed buffer");
   // zero-filled: rows outside every sequence are never stored and the
   // downstream dW GEMMs contract over all T rows
   auto o = torch::zeros({S, H}, qkv.options());
   auto lse = torch::empty({nh, S}, qkv.options().dtype(torch::kFloat));
-  dim3 grid((max_seqlen + 63) / 64, B * nh);
-  auto stream = at::hip::getCurrentHIPStream();
-  const auto* seed_ptr =
-      drop ? (const unsigned long long*)seed_buf.data_ptr() : nullptr;
-
-  DISPATCH_FLOAT_TYPES(qkv.scalar_type(), "flash_attn_varlen_fwd", [&] {
-    if constexpr (!std::is_same<scalar_t, float>::value) {
-      using V8 = std::conditional_t<
-          std::is_same<scalar_t, __hip_bfloat16>::value, bf16x8, f16x8>;
-      if (drop) FA_FWD(false, true, true);
-      else FA_FWD(false, false, true);
-    } else {
-      TORCH_CHECK(false, "flash_attn_varlen: fp32 not supported");
-    }
-  });
+  fa_fwd_launch<true>(qkv, torch::Tensor(), o, lse,
+                      (const int*)cu_seqlens.data_ptr(), max_seqlen, B, S, nh,
+                      scale, p, seed_buf, salt);
   return {o, lse};
 }
 
@@ -958,32 +937,10 @@ torch::Tensor flash_attn_varlen_bwd(torch::Tensor dout, torch::Tensor qkv,
   TORCH_CHECK(o.is_contiguous() && o.sizes() == dout.sizes() &&
                   lse.is_contiguous() && lse.numel() == nh * S,
               "flash_attn_varlen: o [T, H] / lse [nh, T] from the forward");
-  const long seq_max = max_seqlen;
-  const int* cu_ptr = (const int*)cu_seqlens.data_ptr();
-  const bool has_mask = false;
-  torch::Tensor mask;
-  const bool drop = p > 0.0;
   auto dqkv = torch::zeros_like(qkv);  // see flash_attn_varlen_fwd
   auto dvec = torch::empty({nh, S}, qkv.options().dtype(torch::kFloat));
-  dim3 grid((max_seqlen + 63) / 64, B * nh);
-  auto stream = at::hip::getCurrentHIPStream();
-  const auto* seed_ptr =
-      drop ? (const unsigned long long*)seed_buf.data_ptr() : nullptr;
-
-  DISPATCH_FLOAT_TYPES(qkv.scalar_type(), "flash_attn_varlen_bwd", [&] {
-    if constexpr (!std::is_same<scalar_t, float>::value) {
-      using V8 = std::conditional_t<
-          std::is_same<scalar_t, __hip_bfloat16>::value, bf16x8, f16x8>;
-      if (drop) {
-        FA_BWD(fa_bwd_dq_kernel, false, true, true);
-        FA_BWD(fa_bwd_dkv_kernel, false, true, true);
-      } else {
-        FA_BWD(fa_bwd_dq_kernel, false, false, true);
-        FA_BWD(fa_bwd_dkv_kernel, false, false, true);
-      }
-    } else {
-      TORCH_CHECK(false, "flash_attn_varlen: fp32 not supported");
-    }
-  });
+  fa_bwd_launch<true>(dout, qkv, o, lse, torch::Tensor(), dvec, dqkv,
+                      (const int*)cu_seqlens.data_ptr(), max_seqlen, B, S, nh,
+                      scale, p, seed_buf, salt);
   return dqkv;
 }

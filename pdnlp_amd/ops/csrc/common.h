@@ -39,6 +39,29 @@ template <> __device__ __forceinline__ __half from_f32<__half>(float v) {
   return __float2half(v);
 }
 
+// ---- 4-element vector chunk: 8 B for bf16/fp16, 16 B for fp32 -------------
+template <typename T> struct V4 { using type = short4; };
+template <> struct V4<float> { using type = float4; };
+template <typename T> using v4_t = typename V4<T>::type;
+
+template <typename T>
+__device__ __forceinline__ v4_t<T> ld4(const T* p) {
+  return *reinterpret_cast<const v4_t<T>*>(p);
+}
+template <typename T>
+__device__ __forceinline__ void st4(T* p, v4_t<T> v) {
+  *reinterpret_cast<v4_t<T>*>(p) = v;
+}
+// lane j as fp32 / from fp32; T = float addresses the lanes of a float4
+template <typename T>
+__device__ __forceinline__ float elem(const v4_t<T>& v, int j) {
+  return to_f32<T>(reinterpret_cast<const T*>(&v)[j]);
+}
+template <typename T>
+__device__ __forceinline__ void set_elem(v4_t<T>& v, int j, float f) {
+  reinterpret_cast<T*>(&v)[j] = from_f32<T>(f);
+}
+
 // ---- wave reductions (64-wide) --------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -103,6 +126,19 @@ __device__ __forceinline__ float block_sum(float v, float* lds_scratch) {
       }                                                                        \
       default:                                                                 \
         TORCH_CHECK(false, #NAME ": unsupported dtype");                       \
+    }                                                                          \
+  }()
+
+// run the lambda with `constexpr bool NAME` bound to the run-time COND, so a
+// boolean template argument needs one launch call, not one per branch
+#define DISPATCH_BOOL(COND, NAME, ...)                                         \
+  [&] {                                                                        \
+    if (COND) {                                                                \
+      constexpr bool NAME = true;                                              \
+      return __VA_ARGS__();                                                    \
+    } else {                                                                   \
+      constexpr bool NAME = false;                                             \
+      return __VA_ARGS__();                                                    \
     }                                                                          \
   }()
 

@@ -19,28 +19,6 @@
 
 namespace {
 
-// 4-element vector chunk: 8 B for bf16/fp16, 16 B for fp32
-template <typename T> struct V4 { using type = short4; };
-template <> struct V4<float> { using type = float4; };
-template <typename T> using v4_t = typename V4<T>::type;
-
-template <typename T>
-__device__ __forceinline__ v4_t<T> ld4(const T* p) {
-  return *reinterpret_cast<const v4_t<T>*>(p);
-}
-template <typename T>
-__device__ __forceinline__ void st4(T* p, v4_t<T> v) {
-  *reinterpret_cast<v4_t<T>*>(p) = v;
-}
-template <typename T>
-__device__ __forceinline__ float elem(const v4_t<T>& v, int j) {
-  return to_f32<T>(reinterpret_cast<const T*>(&v)[j]);
-}
-template <typename T>
-__device__ __forceinline__ void set_elem(v4_t<T>& v, int j, float f) {
-  reinterpret_cast<T*>(&v)[j] = from_f32<T>(f);
-}
-
 // seed is read from DEVICE memory (seed_base) + a per-call-site salt so the
 // dropout mask changes across hipGraph replays (the host updates *seed_base
 // between replays; a kernel-arg seed would be frozen into the graph).
@@ -257,8 +235,8 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_fwd(
   auto stream = at::hip::getCurrentHIPStream();
   const long grid = (R + 3) / 4;
   DISPATCH_FLOAT_TYPES(y.scalar_type(), "bdrl_fwd", [&] {
-    if (drop) {
-      hipLaunchKernelGGL((bdrl_fwd_kernel<scalar_t, true>), dim3(grid),
+    DISPATCH_BOOL(drop, DROP, [&] {
+      hipLaunchKernelGGL((bdrl_fwd_kernel<scalar_t, DROP>), dim3(grid),
                          dim3(256), 0, stream,
                          (const scalar_t*)y.data_ptr(),
                          (const scalar_t*)bias.data_ptr(),
@@ -267,24 +245,13 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_fwd(
                          (const scalar_t*)lnb.data_ptr(),
                          (scalar_t*)out.data_ptr(),
                          (scalar_t*)xsum.data_ptr(),
-                         mask.data_ptr<unsigned char>(),
+                         DROP ? mask.data_ptr<unsigned char>() : nullptr,
                          mean.data_ptr<float>(), rstd.data_ptr<float>(), H,
                          (float)p, (float)eps,
-                         (const unsigned long long*)seed_buf.data_ptr(),
+                         DROP ? (const unsigned long long*)seed_buf.data_ptr()
+                              : nullptr,
                          (unsigned long long)salt, R);
-    } else {
-      hipLaunchKernelGGL((bdrl_fwd_kernel<scalar_t, false>), dim3(grid),
-                         dim3(256), 0, stream,
-                         (const scalar_t*)y.data_ptr(),
-                         (const scalar_t*)bias.data_ptr(),
-                         (const scalar_t*)res.data_ptr(),
-                         (const scalar_t*)lnw.data_ptr(),
-                         (const scalar_t*)lnb.data_ptr(),
-                         (scalar_t*)out.data_ptr(),
-                         (scalar_t*)xsum.data_ptr(), nullptr,
-                         mean.data_ptr<float>(), rstd.data_ptr<float>(), H,
-                         (float)p, (float)eps, nullptr, 0ull, R);
-    }
+    });
   });
   return {out, xsum, mask, mean, rstd};
 }
@@ -315,26 +282,17 @@ std::vector<torch::Tensor> bdrl_bwd_impl(
   auto accT = torch::empty({(long)KINDS, (long)H}, lnw.options());
   const long grid = (R + 3) / 4;
   DISPATCH_FLOAT_TYPES(xsum.scalar_type(), "bdrl_bwd", [&] {
-    if (drop) {
-      hipLaunchKernelGGL((bdrl_bwd_dx_kernel<scalar_t, true>), dim3(grid),
+    DISPATCH_BOOL(drop, DROP, [&] {
+      hipLaunchKernelGGL((bdrl_bwd_dx_kernel<scalar_t, DROP>), dim3(grid),
                          dim3(256), 0, stream,
                          (const scalar_t*)dout.data_ptr(),
                          (const scalar_t*)xsum.data_ptr(),
-                         mask.data_ptr<unsigned char>(),
+                         DROP ? mask.data_ptr<unsigned char>() : nullptr,
                          (const scalar_t*)lnw.data_ptr(),
                          mean.data_ptr<float>(), rstd.data_ptr<float>(),
                          (scalar_t*)dy.data_ptr(), (scalar_t*)dres.data_ptr(),
                          H, (float)p, R);
-    } else {
-      hipLaunchKernelGGL((bdrl_bwd_dx_kernel<scalar_t, false>), dim3(grid),
-                         dim3(256), 0, stream,
-                         (const scalar_t*)dout.data_ptr(),
-                         (const scalar_t*)xsum.data_ptr(), nullptr,
-                         (const scalar_t*)lnw.data_ptr(),
-                         mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                         (scalar_t*)dy.data_ptr(), (scalar_t*)dres.data_ptr(),
-                         H, 0.f, R);
-    }
+    });
     dim3 g2((H + 63) / 64, chunks);
     hipLaunchKernelGGL((bdrl_bwd_dwdb_kernel<scalar_t, DBIAS>), g2, dim3(256), 0,
                        stream,

@@ -28,23 +28,18 @@ __global__ void bias_gelu_fwd_kernel(const T* __restrict__ x,
   const long stride = (long)gridDim.x * blockDim.x * 8;
   for (long i = i0; i < total; i += stride) {
     if (sizeof(T) == 2 && i + 8 <= total) {
-      short4 r0 = *reinterpret_cast<const short4*>(x + i);
-      short4 r1 = *reinterpret_cast<const short4*>(x + i + 4);
-      const T* px0 = reinterpret_cast<const T*>(&r0);
-      const T* px1 = reinterpret_cast<const T*>(&r1);
-      short4 o0, o1;
-      T* py0 = reinterpret_cast<T*>(&o0);
-      T* py1 = reinterpret_cast<T*>(&o1);
+      const v4_t<T> x0 = ld4(x + i), x1 = ld4(x + i + 4);
+      v4_t<T> y0, y1;
       const int c = (int)(i % N);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        py0[j] = from_f32<T>(
-            gelu_f(to_f32<T>(px0[j]) + to_f32<T>(b[(c + j) % N])));
-        py1[j] = from_f32<T>(
-            gelu_f(to_f32<T>(px1[j]) + to_f32<T>(b[(c + 4 + j) % N])));
+        set_elem<T>(y0, j,
+                    gelu_f(elem<T>(x0, j) + to_f32<T>(b[(c + j) % N])));
+        set_elem<T>(y1, j,
+                    gelu_f(elem<T>(x1, j) + to_f32<T>(b[(c + 4 + j) % N])));
       }
-      *reinterpret_cast<short4*>(y + i) = o0;
-      *reinterpret_cast<short4*>(y + i + 4) = o1;
+      st4(y + i, y0);
+      st4(y + i + 4, y1);
     } else {
       for (long k = i; k < min(i + 8, total); ++k) {
         y[k] = from_f32<T>(gelu_f(to_f32<T>(x[k]) + to_f32<T>(b[k % N])));
@@ -76,24 +71,16 @@ __global__ void gelu_bwd_kernel(const T* __restrict__ dy,
   const long stride = (long)gridDim.x * blockDim.x * 8;
   for (long i = i0; i < total; i += stride) {
     if (sizeof(T) == 2 && i + 8 <= total) {
-      short4 d0 = *reinterpret_cast<const short4*>(dy + i);
-      short4 d1 = *reinterpret_cast<const short4*>(dy + i + 4);
-      short4 p0 = *reinterpret_cast<const short4*>(pre + i);
-      short4 p1 = *reinterpret_cast<const short4*>(pre + i + 4);
-      short4 o0, o1;
-      const T* pd0 = reinterpret_cast<const T*>(&d0);
-      const T* pd1 = reinterpret_cast<const T*>(&d1);
-      const T* pp0 = reinterpret_cast<const T*>(&p0);
-      const T* pp1 = reinterpret_cast<const T*>(&p1);
-      T* po0 = reinterpret_cast<T*>(&o0);
-      T* po1 = reinterpret_cast<T*>(&o1);
+      const v4_t<T> d0 = ld4(dy + i), d1 = ld4(dy + i + 4);
+      const v4_t<T> p0 = ld4(pre + i), p1 = ld4(pre + i + 4);
+      v4_t<T> o0, o1;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        po0[j] = from_f32<T>(to_f32<T>(pd0[j]) * gelu_grad_f(to_f32<T>(pp0[j])));
-        po1[j] = from_f32<T>(to_f32<T>(pd1[j]) * gelu_grad_f(to_f32<T>(pp1[j])));
+        set_elem<T>(o0, j, elem<T>(d0, j) * gelu_grad_f(elem<T>(p0, j)));
+        set_elem<T>(o1, j, elem<T>(d1, j) * gelu_grad_f(elem<T>(p1, j)));
       }
-      *reinterpret_cast<short4*>(dx + i) = o0;
-      *reinterpret_cast<short4*>(dx + i + 4) = o1;
+      st4(dx + i, o0);
+      st4(dx + i + 4, o1);
     } else {
       for (long k = i; k < min(i + 8, total); ++k)
         dx[k] = from_f32<T>(to_f32<T>(dy[k]) * gelu_grad_f(to_f32<T>(pre[k])));
@@ -132,10 +119,9 @@ void col_sum_kernel(const T* __restrict__ x, float* __restrict__ part,
   float s[4] = {};
   if (c0 < N) {
     for (long r = r0 + strip; r < r1; r += 16) {
-      const short4 v = *reinterpret_cast<const short4*>(x + r * N + c0);
-      const T* pv = reinterpret_cast<const T*>(&v);
+      const v4_t<T> v = ld4(x + r * N + c0);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) s[j] += to_f32<T>(pv[j]);
+      for (int j = 0; j < 4; ++j) s[j] += elem<T>(v, j);
     }
   }
 #pragma unroll

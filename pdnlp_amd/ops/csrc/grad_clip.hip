@@ -8,9 +8,8 @@
 // rewritten on the fused path. multi_tensor_scale_ serves the in-place API.
 //
 // Sum of squares, deterministic, no atomics:
-//   stage 1  one block per EPB = 16384 elements of one tensor (same
-//            argument-block packing as adamw.hip: MAXT tensors per launch,
-//            block-prefix scan). A thread makes K 16-byte loads (bf16/fp16:
+//   stage 1  one block per EPB = 16384 elements of one tensor (packing and
+//            launch: multi_tensor.h). A thread makes K 16-byte loads (bf16/fp16:
 //            8 lanes x K=8, fp32: 4 lanes x K=16), strided by the block so
 //            a wave reads contiguous 1-KiB rows, and keeps one fp32
 //            accumulator PER VECTOR LANE. The block writes one fp32 partial
@@ -30,49 +29,51 @@
 //   (L + D) * 2^-24 = 117 * 5.96e-8 = 6.97e-6 <= 1e-5.
 //
 // Alignment: gradients are views into flat DDP/ZeRO buffers at arbitrary
-// element offsets. The host passes `head`, the number of elements before the
-// first 16-byte boundary; those (< 8) are read with scalar loads by block 0,
-// the body behind them is 16-byte aligned, and the last partial vector is
-// read scalar.
-
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
+// element offsets. `head` is the number of elements before the first 16-byte
+// boundary; those (< 8) are read with scalar loads by block 0, the body
+// behind them is 16-byte aligned, and the last partial vector is read scalar.
 
 #include <optional>
 
-#include "common.h"
+#include "multi_tensor.h"
 
 namespace {
 
-constexpr int MAXT = 32;
-constexpr int BLOCK = 256;
+using namespace mt;
+
 constexpr int NW = BLOCK / WAVE;
 constexpr int EPB = 16384;       // elements per stage-1 block, every dtype
 constexpr int FOLD_BLOCK = 1024;
 constexpr int FOLD_NW = FOLD_BLOCK / WAVE;
 constexpr long MAX_PARTIALS = 65536;  // keeps the stage-2 chain at <= 64
 
-struct SumsqMeta {
-  const void* g[MAXT];
-  long numel[MAXT];
-  int head[MAXT];  // elements before the first 16-byte boundary (<= numel)
-  int block_prefix[MAXT + 1];
-  int ntensors;
-};
+// elements of a tensor before the first 16-byte boundary (<= numel)
+__host__ __device__ inline long head_elems(const void* p, long esize,
+                                           long numel) {
+  const long head = (long)(((16ul - ((unsigned long)p & 15ul)) & 15ul) / esize);
+  return head < numel ? head : numel;
+}
+
+// stage-1 blocks of a tensor; one that is all head still needs its block 0
+int sumsq_blocks(const torch::Tensor& t) {
+  const long nb =
+      t.numel() - head_elems(t.data_ptr(), t.element_size(), t.numel());
+  return (int)(nb > 0 ? (nb + EPB - 1) / EPB : 1);
+}
 
 template <typename T>
 __global__ __launch_bounds__(BLOCK)
-void sumsq_partial_kernel(SumsqMeta meta, float* __restrict__ partials) {
+void sumsq_partial_kernel(Meta<1> meta, float* __restrict__ partials) {
   constexpr int VEC = 16 / sizeof(T);
   constexpr int K = EPB / (BLOCK * VEC);
   __shared__ float lds[NW];
-  int t = 0;
-  while (t + 1 < meta.ntensors && blockIdx.x >= meta.block_prefix[t + 1]) ++t;
-  const long local_block = blockIdx.x - meta.block_prefix[t];
-  const int head = meta.head[t];
-  const T* g = (const T*)meta.g[t];
-  const T* body = g + head;              // 16-byte aligned
-  const long nb = meta.numel[t] - head;  // >= 0
+  const Slot slot = find_tensor(meta);
+  const long local_block = slot.local_block;
+  const long numel = meta.numel[slot.t];
+  const T* g = (const T*)meta.ptr[0][slot.t];
+  const int head = (int)head_elems(g, sizeof(T), numel);
+  const T* body = g + head;      // 16-byte aligned
+  const long nb = numel - head;  // >= 0
 
   float acc[VEC];
 #pragma unroll
@@ -161,52 +162,16 @@ __global__ void clip_coef_kernel(const float* __restrict__ sumsq,
 }
 
 // ---- in-place scale by a device scalar -------------------------------------
-constexpr int ILP = 4;
-template <typename TT> struct V4A { using type = short4; };
-template <> struct V4A<float> { using type = float4; };
-template <typename TT> using v4_t = typename V4A<TT>::type;
-
-struct ScaleMeta {
-  void* g[MAXT];
-  long numel[MAXT];
-  int block_prefix[MAXT + 1];
-  int ntensors;
-};
-
 template <typename T>
 __global__ __launch_bounds__(BLOCK)
-void scale_kernel(ScaleMeta meta, const float* __restrict__ coef) {
+void scale_kernel(Meta<1> meta, const float* __restrict__ coef) {
   const float c = *coef;
   // below the clip threshold the coefficient is exactly 1: leave the
   // gradients untouched instead of rewriting them with themselves
   if (c == 1.f) return;
-  int t = 0;
-  while (t + 1 < meta.ntensors && blockIdx.x >= meta.block_prefix[t + 1]) ++t;
-  const long local_block = blockIdx.x - meta.block_prefix[t];
-  const long n = meta.numel[t];
-  T* g = (T*)meta.g[t];
-  const long i0 = (local_block * BLOCK + threadIdx.x) * (long)ILP;
-  if ((((unsigned long)g) & (sizeof(v4_t<T>) - 1)) == 0 && i0 + ILP <= n) {
-    v4_t<T> gv = *reinterpret_cast<const v4_t<T>*>(g + i0);
-#pragma unroll
-    for (int j = 0; j < ILP; ++j)
-      reinterpret_cast<T*>(&gv)[j] =
-          from_f32<T>(to_f32<T>(reinterpret_cast<const T*>(&gv)[j]) * c);
-    *reinterpret_cast<v4_t<T>*>(g + i0) = gv;
-  } else {
-    for (int j = 0; j < ILP; ++j) {
-      const long i = i0 + j;
-      if (i >= n) break;
-      g[i] = from_f32<T>(to_f32<T>(g[i]) * c);
-    }
-  }
-}
-
-float* scalar_ptr(const torch::Tensor& t, const char* name) {
-  TORCH_CHECK(t.defined() && t.is_cuda() && t.numel() == 1 &&
-                  t.scalar_type() == at::ScalarType::Float,
-              name, " must be a 1-element fp32 device tensor");
-  return t.data_ptr<float>();
+  const Slot s = find_tensor(meta);
+  map_inplace((T*)meta.ptr[0][s.t], meta.numel[s.t], s.local_block,
+              [c](float x) { return x * c; });
 }
 
 }  // namespace
@@ -225,18 +190,9 @@ void multi_tensor_sumsq(std::vector<torch::Tensor> tensors, torch::Tensor out,
   }
   auto stream = at::hip::getCurrentHIPStream();
 
-  std::vector<const torch::Tensor*> live;
+  const auto live = live_tensors(tensors, "multi_tensor_sumsq");
   long total_blocks = 0;
-  for (auto& t : tensors) {
-    if (t.numel() == 0) continue;
-    TORCH_CHECK(t.is_cuda() && t.is_contiguous(),
-                "multi_tensor_sumsq: tensors must be contiguous device tensors");
-    if (!live.empty())
-      TORCH_CHECK(t.scalar_type() == live[0]->scalar_type(),
-                  "mixed dtypes in one call");
-    live.push_back(&t);
-    total_blocks += (t.numel() + EPB - 1) / EPB;
-  }
+  for (auto& t : live) total_blocks += (t.numel() + EPB - 1) / EPB;
   TORCH_CHECK(total_blocks <= MAX_PARTIALS,
               "multi_tensor_sumsq: more than ", MAX_PARTIALS * (long)EPB,
               " elements in one call; split the list and accumulate");
@@ -247,38 +203,16 @@ void multi_tensor_sumsq(std::vector<torch::Tensor> tensors, torch::Tensor out,
     partials = torch::empty({total_blocks},
                             out.options().dtype(at::ScalarType::Float));
     partp = partials.data_ptr<float>();
-    const auto dtype = live[0]->scalar_type();
-    const long esize = (long)live[0]->element_size();
-    size_t i = 0;
+    // every launch of the call writes its own slice of the one workspace
     long part_base = 0;
-    while (i < live.size()) {
-      SumsqMeta meta{};
-      int nt = 0;
-      int blocks = 0;
-      while (i < live.size() && nt < MAXT) {
-        const torch::Tensor& t = *live[i];
-        const unsigned long addr = (unsigned long)t.data_ptr();
-        long head = (long)(((16ul - (addr & 15ul)) & 15ul) / esize);
-        if (head > t.numel()) head = t.numel();
-        const long nb = t.numel() - head;
-        meta.g[nt] = t.data_ptr();
-        meta.numel[nt] = t.numel();
-        meta.head[nt] = (int)head;
-        meta.block_prefix[nt] = blocks;
-        // a tensor that is all head still needs its block 0
-        const long b = (nb + EPB - 1) / EPB;
-        blocks += (int)(b > 0 ? b : 1);
-        ++nt;
-        ++i;
-      }
-      meta.block_prefix[nt] = blocks;
-      meta.ntensors = nt;
-      DISPATCH_FLOAT_TYPES(dtype, "multi_tensor_sumsq", [&] {
+    for_each_chunk<1>({&live}, sumsq_blocks, [&](const Meta<1>& meta,
+                                                 int blocks) {
+      DISPATCH_FLOAT_TYPES(live[0].scalar_type(), "multi_tensor_sumsq", [&] {
         hipLaunchKernelGGL((sumsq_partial_kernel<scalar_t>), dim3(blocks),
                            dim3(BLOCK), 0, stream, meta, partp + part_base);
       });
       part_base += blocks;
-    }
+    });
     total_blocks = part_base;
   }
   hipLaunchKernelGGL(sumsq_fold_kernel, dim3(1), dim3(FOLD_BLOCK), 0, stream,
@@ -299,37 +233,13 @@ void multi_tensor_scale_(std::vector<torch::Tensor> tensors,
                          torch::Tensor coef) {
   const float* coefp = scalar_ptr(coef, "coef");
   auto stream = at::hip::getCurrentHIPStream();
-  std::vector<const torch::Tensor*> live;
-  for (auto& t : tensors) {
-    if (t.numel() == 0) continue;
-    TORCH_CHECK(t.is_cuda() && t.is_contiguous(),
-                "multi_tensor_scale_: tensors must be contiguous device tensors");
-    if (!live.empty())
-      TORCH_CHECK(t.scalar_type() == live[0]->scalar_type(),
-                  "mixed dtypes in one call");
-    live.push_back(&t);
-  }
+  const auto live = live_tensors(tensors, "multi_tensor_scale_");
   if (live.empty()) return;
-  const auto dtype = live[0]->scalar_type();
-  size_t i = 0;
-  while (i < live.size()) {
-    ScaleMeta meta{};
-    int nt = 0;
-    int blocks = 0;
-    while (i < live.size() && nt < MAXT) {
-      const torch::Tensor& t = *live[i];
-      meta.g[nt] = t.data_ptr();
-      meta.numel[nt] = t.numel();
-      meta.block_prefix[nt] = blocks;
-      blocks += (int)((t.numel() + (long)BLOCK * ILP - 1) / ((long)BLOCK * ILP));
-      ++nt;
-      ++i;
-    }
-    meta.block_prefix[nt] = blocks;
-    meta.ntensors = nt;
-    DISPATCH_FLOAT_TYPES(dtype, "multi_tensor_scale_", [&] {
-      hipLaunchKernelGGL((scale_kernel<scalar_t>), dim3(blocks), dim3(BLOCK), 0,
-                         stream, meta, coefp);
-    });
-  }
+  for_each_chunk<1>(
+      {&live}, elementwise_blocks, [&](const Meta<1>& meta, int blocks) {
+        DISPATCH_FLOAT_TYPES(live[0].scalar_type(), "multi_tensor_scale_", [&] {
+          hipLaunchKernelGGL((scale_kernel<scalar_t>), dim3(blocks),
+                             dim3(BLOCK), 0, stream, meta, coefp);
+        });
+      });
 }

@@ -33,11 +33,10 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ w,
   float sum = 0.f, sumsq = 0.f;
   if (VEC == 4) {
     for (int base = lane * 4; base < H; base += WAVE * 4) {
-      const short4 raw = *reinterpret_cast<const short4*>(xr + base);
-      const T* px = reinterpret_cast<const T*>(&raw);
+      const v4_t<T> xv = ld4(xr + base);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        float v = to_f32<T>(px[j]) - shift;
+        float v = elem<T>(xv, j) - shift;
         sum += v;
         sumsq += v * v;
       }
@@ -57,20 +56,14 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ w,
   }
   if (VEC == 4) {
     for (int base = lane * 4; base < H; base += WAVE * 4) {
-      const short4 rx = *reinterpret_cast<const short4*>(xr + base);
-      const short4 rw = *reinterpret_cast<const short4*>(w + base);
-      const short4 rb = *reinterpret_cast<const short4*>(b + base);
-      const T* px = reinterpret_cast<const T*>(&rx);
-      const T* pw = reinterpret_cast<const T*>(&rw);
-      const T* pb = reinterpret_cast<const T*>(&rb);
-      short4 ry;
-      T* py = reinterpret_cast<T*>(&ry);
+      const v4_t<T> xv = ld4(xr + base), wv = ld4(w + base), bv = ld4(b + base);
+      v4_t<T> yv;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        float v = (to_f32<T>(px[j]) - shift - md) * rstd;
-        py[j] = from_f32<T>(v * to_f32<T>(pw[j]) + to_f32<T>(pb[j]));
+        float v = (elem<T>(xv, j) - shift - md) * rstd;
+        set_elem<T>(yv, j, v * elem<T>(wv, j) + elem<T>(bv, j));
       }
-      *reinterpret_cast<short4*>(yr + base) = ry;
+      st4(yr + base, yv);
     }
   } else {
     for (int c = lane; c < H; c += WAVE) {
@@ -148,23 +141,15 @@ std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
   auto stream = at::hip::getCurrentHIPStream();
   DISPATCH_FLOAT_TYPES(x.scalar_type(), "layernorm_fwd", [&] {
     const bool vec = !std::is_same<scalar_t, float>::value && (H % 256 == 0);
-    if (vec) {
-      hipLaunchKernelGGL((ln_fwd_kernel<scalar_t, 4>), dim3(R), dim3(WAVE), 0,
-                         stream,
+    DISPATCH_BOOL(vec, VEC4, [&] {
+      hipLaunchKernelGGL((ln_fwd_kernel<scalar_t, VEC4 ? 4 : 1>), dim3(R),
+                         dim3(WAVE), 0, stream,
                          (const scalar_t*)x.data_ptr(),
                          (const scalar_t*)w.data_ptr(),
                          (const scalar_t*)b.data_ptr(),
                          (scalar_t*)y.data_ptr(), mean.data_ptr<float>(),
                          rstd.data_ptr<float>(), H, (float)eps);
-    } else {
-      hipLaunchKernelGGL((ln_fwd_kernel<scalar_t, 1>), dim3(R), dim3(WAVE), 0,
-                         stream,
-                         (const scalar_t*)x.data_ptr(),
-                         (const scalar_t*)w.data_ptr(),
-                         (const scalar_t*)b.data_ptr(),
-                         (scalar_t*)y.data_ptr(), mean.data_ptr<float>(),
-                         rstd.data_ptr<float>(), H, (float)eps);
-    }
+    });
   });
   return {y, mean, rstd};
 }
