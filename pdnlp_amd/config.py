@@ -130,7 +130,7 @@ class Args:
     optimizer: str = "adamw"           # "adamw" | "sgd" (fabric alt-path)
     sgd_momentum: float = 0.9
     lr_scheduler: str = "none"         # "none" | "cosine" | "warmup_linear"
-    hip_graph: bool = False            # capture fwd+bwd into a hipGraph (1 GPU)
+    hip_graph: bool = False            # replay fwd+bwd hipGraphs, one per batch key (1 GPU)
     torch_profile_steps: int = 0       # >0: profile that many steps (after 3
                                        # warmup) to output_dir/trace.json
     warmup_ratio: float = 0.1          # for warmup_linear

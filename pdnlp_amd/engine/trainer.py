@@ -34,6 +34,79 @@ from ..utils.logging import rank0_print
 from ..utils.metrics import MetricsWriter, StepTimer, TraceRange
 
 
+MAX_GRAPHS = 32        # captured graphs kept; further batch keys run eager
+GRAPH_EAGER_STEPS = 3  # eager steps that must have run before any capture
+
+
+def graph_key(batch, max_seq_len: int):
+    """Batch signature under which a captured fwd+bwd graph is replayed.
+
+    Padded batches: ``("padded", B, S)``. Packed batches
+    (``pack_batch``): ``("packed", T, B, ms)`` with ``ms`` the batch's
+    ``max_seqlen`` rounded up to 128 and capped at ``max_seq_len`` — the
+    graph is captured with ``max_seqlen=ms``, so the attention grid and
+    the PRELOAD/streamed choice hold for every batch of the key, whatever
+    its sequence boundaries. ``None``: the batch cannot be replayed (a
+    sequence longer than ``max_seq_len``)."""
+    ids = batch["input_ids"]
+    if "cu_seqlens" not in batch:
+        return ("padded", int(ids.shape[0]), int(ids.shape[1]))
+    longest = int(batch["max_seqlen"])
+    if longest > max_seq_len:
+        return None
+    ms = min(int(max_seq_len), (longest + 127) // 128 * 128)
+    return ("packed", int(ids.numel()),
+            int(batch["cu_seqlens"].numel()) - 1, ms)
+
+
+class GraphPolicy:
+    """When a batch key gets a graph (no device involved): on its second
+    or later sighting, once ``eager_steps`` eager steps have run, while
+    fewer than ``max_graphs`` graphs exist. ``decide`` returns "replay",
+    "capture" (capture now, then replay) or "eager"."""
+
+    def __init__(self, max_graphs: int = MAX_GRAPHS,
+                 eager_steps: int = GRAPH_EAGER_STEPS):
+        self.max_graphs = max_graphs
+        self.eager_steps = eager_steps
+        self.seen = set()
+        self.captured = set()
+        self.eager = 0
+
+    def decide(self, key) -> str:
+        if key in self.captured:
+            return "replay"
+        if (key is not None and key in self.seen
+                and self.eager >= self.eager_steps
+                and len(self.captured) < self.max_graphs):
+            self.captured.add(key)
+            return "capture"
+        self.seen.add(key)
+        self.eager += 1
+        return "eager"
+
+
+class _GraphEntry:
+    """One captured fwd+bwd graph: its static input buffers, the gradient
+    tensors its backward assigns (in ``model.parameters()`` order) and its
+    outputs. All of them stay referenced for the life of the entry, so
+    later captures into the shared pool cannot reuse their memory."""
+
+    def __init__(self, static, label_key):
+        self.static = static
+        self.label_key = label_key
+        self.graph = None
+        self.grads = self.loss = self.logits = None
+
+    def run(self, batch):
+        """Copy ``batch`` into the static buffers and replay. The caller
+        reseeds dropout and owns what happens to ``grads``."""
+        for k, t in self.static.items():
+            t.copy_(batch[k], non_blocking=True)
+        self.graph.replay()
+        return self.loss, self.logits, self.static[self.label_key]
+
+
 class Trainer:
     def __init__(self, args, model, optimizer, device,
                  scaler=None, lr_scheduler=None, label_key: str = "label"):
@@ -51,9 +124,14 @@ class Trainer:
         self.best_acc = -1.0  # first dev eval always checkpoints
         self.global_step = 0
         self._resume_skip = 0  # batches to fast-forward after load_state
-        self._graph = None
-        self._graph_warm = 0
-        self._static = None
+        # hipGraph replay (args.hip_graph): batch key -> _GraphEntry, all
+        # captured into one memory pool; _graph_bound is the entry whose
+        # gradient tensors the parameters' .grad currently point at
+        self._graphs = {}
+        self._graph_policy = GraphPolicy()
+        self._graph_pool = None
+        self._graph_bound = None
+        self.graph_stats = {"captured": 0, "replayed": 0, "eager": 0}
         # global gradient norm of the last optimizer step as an fp32[1]
         # DEVICE tensor (None while max_grad_norm is off); read on logged
         # steps only, where the loss .item() syncs anyway
@@ -213,83 +291,156 @@ class Trainer:
         else:
             self.optimizer.zero_grad(set_to_none=True)
 
-    # ---- hipGraph-captured training step (single GPU, SURVEY.md §5.1+) ----
-    def _maybe_capture_graph(self, batch):
-        """Capture fwd+bwd into a hipGraph after the first eager steps.
+    # ---- hipGraph-replayed training steps (single GPU, SURVEY.md §5.1+) ----
+    # One graph of fwd+bwd per batch key (graph_key), padded and packed
+    # batches alike; the optimizer, the clip and dropout reseeding stay
+    # eager between replays. DESIGN.md "hipGraph replay per batch key".
+    @property
+    def _graph(self):
+        """The graph cache once any graph exists, else None."""
+        return self._graphs or None
 
-        Enabled by ``args.hip_graph`` on a single GPU without grad
-        accumulation: inputs are copied into static device buffers and the
-        graph replayed — kernel-launch-free steps. Grads are captured with
-        set_to_none semantics so every replay OVERWRITES the same blocks
-        (no zero_grad, no accumulate-adds; see bench.py). The optimizer
-        stays eager; dropout reseeds per replay via the device seed."""
-        if self._graph is not None:
-            return True
-        if getattr(self.args, "hip_graph", False) \
-                and getattr(self.args, "unpad", False):
-            # the packed token count changes every step: nothing to replay
-            if not getattr(self, "_unpad_graph_noted", False):
+    def _graph_capable(self) -> bool:
+        a = self.args
+        return (self.device.type == "cuda" and self.world == 1
+                and getattr(a, "grad_accum_steps", 1) <= 1
+                and self.scaler is None
+                and not getattr(a, "activation_checkpointing", False)
+                and not isinstance(self.model, DistributedDataParallel)
+                and not isinstance(self.optimizer, ZeroRedundancyOptimizer))
+
+    def _graph_key(self, batch):
+        return graph_key(batch, int(getattr(self.args, "max_seq_len", 128)))
+
+    def _maybe_capture_graph(self, batch):
+        """True when ``batch`` has a graph to replay, capturing one first
+        where GraphPolicy says so. Enabled by ``args.hip_graph`` on a
+        single GPU without grad accumulation, fp16 scaling or activation
+        checkpointing."""
+        if not getattr(self.args, "hip_graph", False):
+            return False
+        if not self._graph_capable():
+            if getattr(self.args, "unpad", False) \
+                    and not getattr(self, "_unpad_graph_noted", False):
                 self._unpad_graph_noted = True
-                rank0_print("[pdnlp] --unpad: token shapes vary per step, "
-                            "hipGraph capture disabled (eager steps)")
+                rank0_print("[pdnlp] --unpad with --hip-graph needs one GPU, "
+                            "no grad accumulation, no fp16 scaler and no "
+                            "activation checkpointing: hipGraph capture "
+                            "disabled (eager steps)")
             return False
-        if not (getattr(self.args, "hip_graph", False)
-                and torch.cuda.is_available() and self.world == 1
-                and getattr(self.args, "grad_accum_steps", 1) <= 1
-                and self.scaler is None):
-            return False
-        if self._graph_warm < 3:   # eager warmup steps before capture
-            self._graph_warm += 1
-            return False
-        keys = ("input_ids", "attention_mask", "token_type_ids",
-                self.label_key)
-        self._static = {k: batch[k].to(self.device).clone() for k in keys}
+        key = self._graph_key(batch)
+        what = self._graph_policy.decide(key)
+        if what == "capture":
+            self._graphs[key] = self._capture_graph(batch, key)
+            self.graph_stats["captured"] += 1
+            rank0_print(f"[pdnlp] hipGraph captured for {key}: replaying "
+                        f"fwd+bwd ({len(self._graphs)} graphs)")
+        return what != "eager"
+
+    def _model_inputs(self, static, key):
+        kw = dict(input_ids=static["input_ids"],
+                  token_type_ids=static["token_type_ids"],
+                  labels=static[self.label_key])
+        if key[0] == "packed":
+            # max_seqlen is the key's bound, not the batch's own maximum:
+            # the captured attention launch must cover every batch of the key
+            kw.update(cu_seqlens=static["cu_seqlens"], max_seqlen=key[3],
+                      position_ids=static["position_ids"])
+        else:
+            kw.update(attention_mask=static["attention_mask"])
+        return kw
+
+    def _release_graph_grads(self):
+        """Unbind .grad from a replayed graph's tensors, so that an eager
+        backward (or a capture) assigns fresh gradients instead of
+        accumulating onto the last replay's."""
+        if self._graph_bound is not None:
+            self._graph_bound = None
+            for p in self.model.parameters():
+                p.grad = None
+
+    def _capture_graph(self, batch, key=None):
+        """Capture fwd+bwd on ``batch`` into a new _GraphEntry. The caller
+        holds no autograd references of an earlier step (see the note at
+        ``del out``). Gradients are captured with .grad = None, so the
+        backward ASSIGNS them: every replay overwrites the entry's own
+        gradient tensors (no zero_grad, no accumulate-adds)."""
+        key = key or self._graph_key(batch)
+        names = ["input_ids", "token_type_ids", self.label_key]
+        names += ["cu_seqlens", "position_ids"] if key[0] == "packed" \
+            else ["attention_mask"]
+        entry = _GraphEntry({k: batch[k].to(self.device).clone()
+                             for k in names}, self.label_key)
+        inputs = self._model_inputs(entry.static, key)
+        params = list(self.model.parameters())
+        self._release_graph_grads()
+        # warm-up: forward and backward only — an optimizer step here would
+        # be an update on this batch that no step counter sees
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(2):
-                out = self.model(
-                    input_ids=self._static["input_ids"],
-                    attention_mask=self._static["attention_mask"],
-                    token_type_ids=self._static["token_type_ids"],
-                    labels=self._static[self.label_key])
+                out = self.model(**inputs)
                 out.loss.backward()
-                self._optimizer_step()
         del out  # a live autograd graph from before the capture pins
         #          default/side-stream AccumulateGrad nodes and SEGFAULTS
         #          hipGraph instantiation (torch input_buffer stream check)
         torch.cuda.current_stream().wait_stream(s)
-        self.optimizer.zero_grad(set_to_none=True)
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            out = self.model(
-                input_ids=self._static["input_ids"],
-                attention_mask=self._static["attention_mask"],
-                token_type_ids=self._static["token_type_ids"],
-                labels=self._static[self.label_key])
+        for p in params:
+            p.grad = None
+        if self._graph_pool is None:
+            self._graph_pool = torch.cuda.graph_pool_handle()
+        entry.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(entry.graph, pool=self._graph_pool):
+            out = self.model(**inputs)
             out.loss.backward()
-            self._static_loss = out.loss
-            self._static_logits = out.logits
-        rank0_print("[pdnlp] hipGraph captured: replaying fwd+bwd")
-        return True
+        # detached: the outputs must not keep the captured autograd graph
+        # (and its AccumulateGrad nodes) alive into the next capture
+        entry.loss, entry.logits = out.loss.detach(), out.logits.detach()
+        del out
+        entry.grads = [p.grad for p in params]
+        for p in params:   # bound again by the first replay
+            p.grad = None
+        return entry
 
     def _graph_step(self, batch):
+        """Replay the graph of ``batch``'s key and step the optimizer;
+        None when the key has no graph (the caller runs the step eager).
+        .grad stays bound to the entry's gradients afterwards."""
         from ..ops import reseed_dropout
-        for k, t in self._static.items():
-            if batch[k].shape != t.shape:
-                return None  # tail batch with a different shape: run eager
-        for k, t in self._static.items():
-            t.copy_(batch[k].to(self.device, non_blocking=True),
-                    non_blocking=True)
+        entry = self._graphs.get(self._graph_key(batch))
+        if entry is None:
+            return None
         reseed_dropout()
-        self._graph.replay()
-        # grads overwritten in-place by the replay; the clip runs eagerly
-        # between replay and step, like the optimizer itself
+        res = entry.run(batch)
+        if self._graph_bound is not entry:
+            for p, g in zip(self.model.parameters(), entry.grads):
+                p.grad = g
+            self._graph_bound = entry
+        # the clip runs eagerly between replay and step, like the optimizer
         self._optimizer_step()
         if self.lr_scheduler is not None:
             self.lr_scheduler.step()
-        return (self._static_loss, self._static_logits,
-                self._static[self.label_key])
+        self.graph_stats["replayed"] += 1
+        return res
+
+    def train_step(self, batch, accum_boundary: bool = True):
+        """One training step on ``batch``: a graph replay where its key has
+        a graph, an eager step otherwise. Returns (loss, logits, labels,
+        stepped). The caller drops the previous step's loss/logits first:
+        a capture must not find their autograd graph alive."""
+        if self._maybe_capture_graph(batch):
+            res = self._graph_step(batch)
+            if res is not None:
+                return (*res, True)
+        self._release_graph_grads()
+        with TraceRange("forward"):
+            loss, logits, labels = self.on_step(batch)
+        if self.args.barrier_per_step and self.world > 1:
+            dist.barrier()
+        stepped = self._backward_and_step(loss, accum_boundary)
+        self.graph_stats["eager"] += 1
+        return loss, logits, labels, stepped
 
     def _state_path(self) -> str:
         import os
@@ -374,23 +525,10 @@ class Trainer:
                 micro += 1
                 accum_boundary = (micro % max(args.grad_accum_steps, 1) == 0)
                 # drop the previous step's autograd references BEFORE any
-                # capture attempt (see note in _maybe_capture_graph)
+                # capture attempt (see note in _capture_graph)
                 loss = logits = None
-                if self._maybe_capture_graph(batch):
-                    res = self._graph_step(batch)
-                    if res is not None:
-                        loss, logits, labels = res
-                        stepped = True
-                        self.global_step += 1
-                        timer.step(labels.shape[0] * self.world)
-                        self._after_step(epoch, total_step, loss, timer,
-                                         dev_loader, stepped)
-                        continue
-                with TraceRange("forward"):
-                    loss, logits, labels = self.on_step(batch)
-                if args.barrier_per_step and self.world > 1:
-                    dist.barrier()
-                stepped = self._backward_and_step(loss, accum_boundary)
+                loss, logits, labels, stepped = self.train_step(
+                    batch, accum_boundary)
                 self.global_step += 1
                 timer.step(labels.shape[0] * self.world)
                 self._after_step(epoch, total_step, loss, timer, dev_loader,
@@ -405,7 +543,8 @@ class Trainer:
         mins = (time.time() - t_start) / 60.0
         rank0_print(f"耗时：{mins:.4f}分钟 (wall-clock minutes)")
         self.metrics.write(phase="train_end", minutes=mins,
-                           samples_per_sec=timer.samples_per_sec(sync=True))
+                           samples_per_sec=timer.samples_per_sec(sync=True),
+                           graph_stats=dict(self.graph_stats))
         return mins
 
     def _after_step(self, epoch, total_step, loss, timer, dev_loader,

@@ -18,8 +18,16 @@ a new shape). Timed windows of ``--steps`` steps alternate padded / unpad,
 reports every window, the range per mode and whether the ranges are
 disjoint, then ``torch.cuda.memory_reserved()`` after ``--mem-steps`` steps
 per mode (allocator cache emptied in between), and one JSON line.
+
+A third mode, ``unpad_graph``, runs the same packed batches through the
+Trainer's hipGraph cache (``--unpad true --hip-graph true``) in the same
+alternating windows. After the eager pass it passes over the pool twice
+more with capture on, so that
+every batch key is captured and the timed windows hold replays only, and
+reports what the graphs' shared memory pool holds.
 """
 import argparse
+import gc
 import json
 import math
 import os
@@ -29,7 +37,9 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pdnlp_amd.config import Args  # noqa: E402
 from pdnlp_amd.data import load_data, pack_batch  # noqa: E402
+from pdnlp_amd.engine.trainer import Trainer  # noqa: E402
 from pdnlp_amd.models import build_model  # noqa: E402
 from pdnlp_amd.ops.adamw import build_optimizer  # noqa: E402
 from pdnlp_amd.utils import set_seed  # noqa: E402
@@ -101,12 +111,50 @@ class Mode:
     def window(self, steps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        loss = None
         for _ in range(steps):
+            # an eager step's loss keeps its autograd graph alive, and a
+            # graph capture must not find one (Trainer.train_step)
+            del loss
             loss = self.step()
         torch.cuda.synchronize()
         ms = (time.perf_counter() - t0) * 1e3 / steps
         assert math.isfinite(loss.item()), f"{self.name}: loss {loss.item()}"
         return ms
+
+
+class GraphMode(Mode):
+    """The packed batches through the Trainer's hipGraph cache
+    (``--unpad true --hip-graph true``): one captured graph per batch key,
+    eager fused AdamW between replays."""
+
+    def __init__(self, name, batches, dev):
+        super().__init__(name, batches, dev)
+        args = Args()
+        args.unpad = True
+        args.hip_graph = False      # until capture_all()
+        args.max_seq_len = S
+        self.trainer = Trainer(args, self.model, self.opt, dev)
+
+    def capture_all(self):
+        """Two passes over the pool with capture on: a key is captured at
+        its second sighting, so every later step is a replay. Returns the
+        bytes the graphs' memory pool holds (``empty_cache`` on both sides
+        releases what the eager steps cached, never a live graph's pool)."""
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        base = torch.cuda.memory_reserved()
+        self.trainer.args.hip_graph = True
+        for _ in range(2):
+            self.window(len(self.batches))
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        return torch.cuda.memory_reserved() - base
+
+    def step(self):
+        b = self.batches[self.i % len(self.batches)]
+        self.i += 1
+        return self.trainer.train_step(b)[0]
 
 
 def main():
@@ -136,25 +184,38 @@ def main():
           f"{sum(rows) / len(rows):.0f} (max {max(rows)}, "
           f"{len(set(rows))} distinct) vs {a.batch * S} padded rows")
 
+    dev_packed = [to_device(b, dev) for b in packed]
+    graph = GraphMode("unpad_graph", dev_packed, dev)
     modes = [Mode("padded", [to_device(b, dev) for b in padded], dev),
-             Mode("unpad", [to_device(b, dev) for b in packed], dev)]
+             Mode("unpad", dev_packed, dev), graph]
     for m in modes:                      # every shape of the pool, once
         m.window(len(m.batches))
+    graph_pool = graph.capture_all()
+    keys = {graph.trainer._graph_key(b) for b in graph.batches}
+    captured = graph.trainer.graph_stats["captured"]
+    print(f"unpad_graph: {captured} graphs captured for {len(keys)} batch "
+          f"keys; their memory pool holds {graph_pool / 2**20:.0f} MiB")
+    assert captured == len(keys), "timed windows would contain eager steps"
+    eager_before = graph.trainer.graph_stats["eager"]
     times = {m.name: [] for m in modes}
     for p in range(a.pairs):
         for m in modes:
             times[m.name].append(m.window(a.steps))
         print(f"pair {p}: padded {times['padded'][-1]:.3f} ms/step, "
               f"unpad {times['unpad'][-1]:.3f} ms/step")
+        print(f"pair {p}: unpad_graph {times['unpad_graph'][-1]:.3f} ms/step")
+    assert graph.trainer.graph_stats["eager"] == eager_before
     rng = {k: (min(v), max(v)) for k, v in times.items()}
     disjoint = rng["unpad"][1] < rng["padded"][0]
+    graph_disjoint = rng["unpad_graph"][1] < rng["unpad"][0]
     for k, (lo, hi) in rng.items():
         print(f"{k}: {lo:.3f} .. {hi:.3f} ms/step over {a.pairs} windows "
               f"of {a.steps} steps")
     print("ranges disjoint in favour of unpad:", disjoint)
+    print("ranges disjoint in favour of unpad_graph over unpad:",
+          graph_disjoint)
 
-    reserved = {}
-    for m in modes:
+    def measure(m):
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
         base = torch.cuda.memory_reserved()
@@ -167,6 +228,16 @@ def main():
               f"{mid / 2**20:.0f} MiB after {a.mem_steps // 2} steps, "
               f"{reserved[m.name]['end'] / 2**20:.0f} MiB after "
               f"{a.mem_steps}")
+
+    reserved = {}
+    # the graph mode first (all three modes resident), then the other two
+    # without it: its pool stays reserved for as long as its graphs live
+    # and is no part of their figures
+    measure(modes.pop())
+    del graph, m
+    gc.collect()
+    for m in modes:
+        measure(m)
     print(json.dumps({
         "metric": "bench_unpad", "source": source, "batch": a.batch,
         "multiple": a.multiple, "mean_tokens": sum(toks) / len(toks),
@@ -174,7 +245,11 @@ def main():
         "range_ms": rng, "disjoint": disjoint,
         "speedup_of_medians": sorted(times["padded"])[a.pairs // 2]
         / sorted(times["unpad"])[a.pairs // 2],
-        "memory_reserved": reserved}))
+        "memory_reserved": reserved,
+        "graphs_captured": captured, "graph_pool_bytes": graph_pool,
+        "graph_disjoint": graph_disjoint,
+        "graph_speedup_of_medians": sorted(times["unpad"])[a.pairs // 2]
+        / sorted(times["unpad_graph"])[a.pairs // 2]}))
 
 
 if __name__ == "__main__":
