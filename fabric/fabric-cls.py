@@ -44,6 +44,10 @@ def main():
     args.optimizer = ns.optimizer
     args.lr_scheduler = "cosine" if ns.optimizer == "sgd" else "none"
     args.apply_cli(rest)
+    if args.max_tokens > 0:
+        raise SystemExit("--max-tokens is not supported by this entrypoint "
+                         "(its own loop feeds padded [B, S] batches); use "
+                         "single-gpu-cls.py or a multi-gpu-*-cls.py script")
     if args.unpad:
         raise SystemExit("--unpad true is not supported by this entrypoint "
                          "(its own loop feeds padded [B, S] batches); use "

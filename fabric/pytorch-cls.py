@@ -24,6 +24,10 @@ def main():
     args.data_path = os.path.join(os.path.dirname(__file__), "..", "data",
                                   "train.json")
     args.apply_cli()
+    if args.max_tokens > 0:
+        raise SystemExit("--max-tokens is not supported by this entrypoint "
+                         "(its own loop feeds padded [B, S] batches); use "
+                         "single-gpu-cls.py or a multi-gpu-*-cls.py script")
     if args.unpad:
         raise SystemExit("--unpad true is not supported by this entrypoint "
                          "(its own loop feeds padded [B, S] batches); use "

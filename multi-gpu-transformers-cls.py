@@ -55,6 +55,7 @@ def main():
                           **_unpad_kw(base))
     model = build_model(base.model, model_path=base.model_path)
     hf_args.unpad = base.unpad
+    hf_args.max_tokens = base.max_tokens
     trainer = HFStyleTrainer(model, hf_args, train_dataset=train_ds,
                              eval_dataset=dev_ds, data_collator=collate,
                              compute_metrics=compute_metrics)

@@ -18,10 +18,11 @@ import torch
 from torch.utils.data import DataLoader
 
 from .config import Args
-from .data import (ClsDataset, Collate, DistributedSampler, LABELS,
-                   SyntheticClsDataset, build_tokenizer, load_data,
+from .data import (SEQ_MULTIPLE, ClsDataset, Collate, DistributedSampler,
+                   LABELS, SyntheticClsDataset, TokenBudgetBatchSampler,
+                   build_tokenizer, load_data, sequence_lengths,
                    train_dev_split)
-from .engine.trainer import build_training
+from .engine.trainer import build_training, check_token_budget
 from .parallel.bootstrap import cleanup, init_distributed, spawn
 from .utils import set_seed
 from .utils.checkpoint import load_checkpoint
@@ -38,7 +39,32 @@ def _unpad_kw(args: Args) -> dict:
                 pad_token_id=1 if roberta else 0, roberta=roberta)
 
 
+def token_budget_loader(args: Args, dataset, collate: Collate,
+                        world_size: int, rank: int):
+    """Train loader of ``--max-tokens N``: a TokenBudgetBatchSampler over the
+    samples' real lengths and a collate that emits fixed-shape packed
+    batches (N rows, sequence count rounded up to SEQ_MULTIPLE). Returns
+    (loader, sampler); the sampler takes ``set_epoch``."""
+    lengths = sequence_lengths(dataset, collate.tokenizer, args.max_seq_len)
+    sampler = TokenBudgetBatchSampler(
+        lengths, args.max_tokens, getattr(args, "max_sentences", 0),
+        shuffle=True, seed=args.seed, num_replicas=world_size, rank=rank)
+    budget = Collate(collate.tokenizer, collate.max_seq_len,
+                     label_key=collate.label_key, unpad=True,
+                     pad_token_id=collate.pad_token_id,
+                     roberta=collate.roberta, max_tokens=args.max_tokens,
+                     seq_multiple=SEQ_MULTIPLE)
+    rank0_print(f"[data] --max-tokens {args.max_tokens}: {len(lengths)} "
+                f"samples in {len(sampler.batches)} batches of up to "
+                f"{args.max_tokens} packed rows; train_batch_size is not used")
+    loader = DataLoader(dataset, batch_sampler=sampler, collate_fn=budget,
+                        num_workers=args.num_workers,
+                        pin_memory=torch.cuda.is_available())
+    return loader, sampler
+
+
 def build_dataloaders(args: Args, world_size: int, rank: int):
+    check_token_budget(args)
     vocab_size = _VOCAB.get(getattr(args, "model", "bert-base"), 21128)
     if os.path.isfile(args.data_path):
         data = load_data(args.data_path, limit=args.data_limit)
@@ -69,15 +95,19 @@ def build_dataloaders(args: Args, world_size: int, rank: int):
         collate = Collate(None, args.max_seq_len, **_unpad_kw(args))
 
     train_sampler = None
-    if world_size > 1:
-        train_sampler = DistributedSampler(train_ds, num_replicas=world_size,
-                                           rank=rank, shuffle=True,
-                                           seed=args.seed)
-    train_loader = DataLoader(
-        train_ds, batch_size=args.train_batch_size,
-        sampler=train_sampler, shuffle=(train_sampler is None),
-        collate_fn=collate, num_workers=args.num_workers,
-        pin_memory=torch.cuda.is_available(), drop_last=False)
+    if getattr(args, "max_tokens", 0) > 0:
+        train_loader, train_sampler = token_budget_loader(
+            args, train_ds, collate, world_size, rank)
+    else:
+        if world_size > 1:
+            train_sampler = DistributedSampler(
+                train_ds, num_replicas=world_size, rank=rank, shuffle=True,
+                seed=args.seed)
+        train_loader = DataLoader(
+            train_ds, batch_size=args.train_batch_size,
+            sampler=train_sampler, shuffle=(train_sampler is None),
+            collate_fn=collate, num_workers=args.num_workers,
+            pin_memory=torch.cuda.is_available(), drop_last=False)
     dev_sampler = None
     if world_size > 1:
         dev_sampler = DistributedSampler(dev_ds, num_replicas=world_size,

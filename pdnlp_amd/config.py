@@ -110,6 +110,11 @@ class Args:
     unpad: bool = False                # padding-free batches: pack the real
                                        # tokens into one [T] stream (collate)
                                        # + variable-length attention
+    max_tokens: int = 0                # with unpad: batch to a budget of N
+                                       # packed rows per step instead of
+                                       # train_batch_size sentences (0 = off)
+    max_sentences: int = 0             # cap on sentences per budgeted batch
+                                       # (0 = none)
 
     # optimization
     train_batch_size: int = 32         # per GPU

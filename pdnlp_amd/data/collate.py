@@ -12,9 +12,16 @@ from __future__ import annotations
 
 import torch
 
+# sequence-count granule of token-budget batches (``--max-tokens``): the
+# count is rounded up to it with empty sequences, so an epoch has two or
+# three hipGraph keys instead of one per distinct count
+SEQ_MULTIPLE = 32
+IGNORE_LABEL = -100  # label of an empty sequence; the loss skips the row
+
 
 def pack_batch(batch, multiple: int = 64, label_key: str = "label",
-               pad_token_id: int = 0, roberta: bool = False):
+               pad_token_id: int = 0, roberta: bool = False,
+               total_rows=None, seq_multiple=None):
     """Padded batch dict ([B, S] ids/mask/types + labels) -> packed token
     stream for the padding-free path (``--unpad``).
 
@@ -25,6 +32,14 @@ def pack_batch(batch, multiple: int = 64, label_key: str = "label",
     the sequence boundaries, ``max_seqlen`` the longest sequence (a host int,
     so the attention launch needs no device sync). Position ids restart per
     sequence; RoBERTa's are ``pad_token_id + 1 + i`` as on the padded path.
+
+    Fixed shapes (token-budget batching): ``total_rows=N`` pads the stream
+    to exactly N rows and raises ``ValueError`` when the batch holds more
+    real tokens. ``seq_multiple=m`` rounds the sequence count up to a
+    multiple of m with EMPTY sequences: ``cu_seqlens`` repeats the total for
+    them (length 0: the attention kernels exit at once) and their labels
+    are -100 (the loss ignores them). ``max_seqlen`` stays the longest real
+    sequence; ``num_seqs`` is the count of real sequences (a host int).
     """
     mask = batch["attention_mask"]
     B, S = mask.shape
@@ -35,10 +50,22 @@ def pack_batch(batch, multiple: int = 64, label_key: str = "label",
                          "prefix of ones followed by zeros")
     if int(lens.min()) < 1:
         raise ValueError("pack_batch: every sequence needs >= 1 real token")
-    cu = torch.zeros(B + 1, dtype=torch.int32)
-    cu[1:] = lens.cumsum(0)
-    total = int(cu[-1])
-    T = (total + multiple - 1) // multiple * multiple
+    Bp = B if not seq_multiple else \
+        (B + seq_multiple - 1) // seq_multiple * seq_multiple
+    cu = torch.zeros(Bp + 1, dtype=torch.int32)
+    cu[1:B + 1] = lens.cumsum(0)
+    total = int(cu[B])
+    cu[B + 1:] = total
+    if total_rows is None:
+        T = (total + multiple - 1) // multiple * multiple
+    else:
+        T = int(total_rows)
+        if total > T:
+            raise ValueError(f"pack_batch: {total} real tokens do not fit "
+                             f"into total_rows={T}")
+    labels = batch[label_key]
+    if Bp > B:
+        labels = torch.cat([labels, labels.new_full((Bp - B,), IGNORE_LABEL)])
     keep = mask.bool()
     pos = torch.arange(S)[None, :].expand(B, S)[keep]
     if roberta:
@@ -55,27 +82,34 @@ def pack_batch(batch, multiple: int = 64, label_key: str = "label",
         "position_ids": position_ids,
         "cu_seqlens": cu,
         "max_seqlen": int(lens.max()),
-        label_key: batch[label_key],
+        "num_seqs": B,
+        label_key: labels,
     }
 
 
 class Collate:
     def __init__(self, tokenizer, max_seq_len: int = 128,
                  label_key: str = "label", unpad: bool = False,
-                 pad_token_id: int = 0, roberta: bool = False):
+                 pad_token_id: int = 0, roberta: bool = False,
+                 max_tokens=None, seq_multiple=None):
         self.tokenizer = tokenizer
         self.max_seq_len = max_seq_len
         self.label_key = label_key  # HF-Trainer mode uses "labels"
         self.unpad = unpad          # emit the packed stream (pack_batch)
         self.pad_token_id = pad_token_id
         self.roberta = roberta
+        # fixed-shape packed batches (token-budget batching); unpad only
+        self.max_tokens = max_tokens or None
+        self.seq_multiple = seq_multiple or None
 
     def __call__(self, batch):
         out = self.collate_fn(batch)
         if self.unpad:
             out = pack_batch(out, label_key=self.label_key,
                              pad_token_id=self.pad_token_id,
-                             roberta=self.roberta)
+                             roberta=self.roberta,
+                             total_rows=self.max_tokens,
+                             seq_multiple=self.seq_multiple)
         return out
 
     def collate_fn(self, batch):

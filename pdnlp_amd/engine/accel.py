@@ -15,7 +15,7 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader
 
 from ..amp import GradScaler, cast_model_to
-from ..data.sampler import DistributedSampler
+from ..data.sampler import DistributedSampler, TokenBudgetBatchSampler
 from ..parallel.bootstrap import init_distributed
 from ..parallel.ddp import DistributedDataParallel
 
@@ -74,6 +74,14 @@ class Accelerator:
     def _prepare_loader(self, loader: DataLoader) -> DataLoader:
         if not dist.is_initialized():
             return loader
+        if isinstance(loader.batch_sampler, TokenBudgetBatchSampler):
+            # token-budget loader: batch_size is None; shard the batches
+            shard = loader.batch_sampler.shard(dist.get_world_size(),
+                                               dist.get_rank())
+            return DataLoader(loader.dataset, batch_sampler=shard,
+                              num_workers=loader.num_workers,
+                              collate_fn=loader.collate_fn,
+                              pin_memory=loader.pin_memory)
         sampler = DistributedSampler(loader.dataset,
                                      shuffle=not isinstance(
                                          loader.sampler,

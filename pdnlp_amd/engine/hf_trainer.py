@@ -46,6 +46,9 @@ class TrainingArguments:
     gradient_accumulation_steps: int = 1
     dataloader_num_workers: int = 2
     unpad: bool = False   # the data_collator packs (Collate(unpad=True))
+    max_tokens: int = 0   # with unpad: token-budget train batches of this
+                          # many packed rows (per_device_train_batch_size
+                          # is then not used); 0 = off
     # global-norm gradient clipping, 0 = off. HF's own default is 1.0 (so
     # the reference's transformers run clips); set 1.0 to reproduce it.
     max_grad_norm: float = 0.0
@@ -77,6 +80,7 @@ class HFStyleTrainer:
         eargs.grad_accum_steps = args.gradient_accumulation_steps
         eargs.seed = args.seed
         eargs.unpad = args.unpad
+        eargs.max_tokens = args.max_tokens
         eargs.max_grad_norm = args.max_grad_norm
         eargs.output_dir = args.output_dir
         eargs.ckpt_path = os.path.join(args.output_dir, "best_model.pt")
@@ -122,9 +126,24 @@ class HFStyleTrainer:
                           collate_fn=self.data_collator,
                           num_workers=self.hf_args.dataloader_num_workers), sampler
 
+    def _budget_loader(self):
+        """Train loader of ``max_tokens``: a rank-sharded batch sampler and
+        the data_collator's fixed-shape variant."""
+        from ..cli import token_budget_loader
+        import torch.distributed as dist
+        world = dist.get_world_size() if dist.is_initialized() else 1
+        rank = dist.get_rank() if dist.is_initialized() else 0
+        self.args.num_workers = self.hf_args.dataloader_num_workers
+        return token_budget_loader(self.args, self.train_dataset,
+                                   self.data_collator, world, rank)
+
     def train(self):
-        loader, sampler = self._loader(
-            self.train_dataset, self.hf_args.per_device_train_batch_size, True)
+        if self.hf_args.max_tokens > 0:
+            loader, sampler = self._budget_loader()
+        else:
+            loader, sampler = self._loader(
+                self.train_dataset,
+                self.hf_args.per_device_train_batch_size, True)
         eval_loader = None
         if self.eval_dataset is not None:
             eval_loader, _ = self._loader(

@@ -530,7 +530,10 @@ class Trainer:
                 loss, logits, labels, stepped = self.train_step(
                     batch, accum_boundary)
                 self.global_step += 1
-                timer.step(labels.shape[0] * self.world)
+                # budgeted batches round the sequence count up with empty
+                # sequences: count the real ones
+                timer.step(int(batch.get("num_seqs", labels.shape[0]))
+                           * self.world)
                 self._after_step(epoch, total_step, loss, timer, dev_loader,
                                  stepped)
         if prof is not None:
@@ -601,8 +604,9 @@ class Trainer:
             loss, logits, labels = self.on_step(batch)
             total_loss += self.loss_reduce(loss).item()
             g_logits, g_labels = self.output_reduce(logits.float(), labels)
-            preds.append(g_logits.argmax(-1).cpu().numpy())
-            trues.append(g_labels.cpu().numpy())
+            real = g_labels != -100  # empty sequences of a budgeted batch
+            preds.append(g_logits[real].argmax(-1).cpu().numpy())
+            trues.append(g_labels[real].cpu().numpy())
         preds = np.concatenate(preds)
         trues = np.concatenate(trues)
         acc = float((preds == trues).mean()) if len(trues) else 0.0
@@ -619,8 +623,9 @@ class Trainer:
             loss, logits, labels = self.on_step(batch)
             total_loss += self.loss_reduce(loss).item()
             g_logits, g_labels = self.output_reduce(logits.float(), labels)
-            preds.append(g_logits.argmax(-1).cpu().numpy())
-            trues.append(g_labels.cpu().numpy())
+            real = g_labels != -100  # empty sequences of a budgeted batch
+            preds.append(g_logits[real].argmax(-1).cpu().numpy())
+            trues.append(g_labels[real].cpu().numpy())
         preds = np.concatenate(preds)
         trues = np.concatenate(trues)
         report = classification_report_text(trues, preds, label_names)
@@ -676,6 +681,28 @@ def classification_report_text(trues, preds, label_names=None) -> str:
         return "\n".join(lines)
 
 
+def check_token_budget(args) -> None:
+    """Reject configurations ``--max-tokens`` cannot serve (ValueError)."""
+    max_tokens = int(getattr(args, "max_tokens", 0) or 0)
+    if max_tokens > 0:
+        if not getattr(args, "unpad", False):
+            raise ValueError(
+                "--max-tokens needs --unpad true: a token budget batches the "
+                "packed stream, which padded [B, S] batches do not have.")
+        if args.strategy == "dp":
+            raise ValueError(
+                "--max-tokens cannot be combined with strategy=dp (packed "
+                "batches have no dim 0 to split). Use strategy=ddp.")
+        if max_tokens < args.max_seq_len:
+            raise ValueError(
+                f"--max-tokens {max_tokens} is below --max-seq-len "
+                f"{args.max_seq_len}: the longest sentence must fit a batch.")
+        if max_tokens % 64:
+            raise ValueError(
+                f"--max-tokens {max_tokens} must be a multiple of 64, the "
+                f"row granule of the packed stream.")
+
+
 def build_training(args, model=None, label_key: str = "label"):
     """Assemble (model, optimizer, scaler, trainer) for a strategy mode.
 
@@ -696,6 +723,7 @@ def build_training(args, model=None, label_key: str = "label"):
             "--unpad true cannot be combined with strategy=dp: single-process "
             "DataParallel splits the batch on dim 0, which a packed token "
             "stream does not have. Use strategy=ddp (one process per GPU).")
+    check_token_budget(args)
     ndev = max(torch.cuda.device_count(), 1)
     device = torch.device(f"cuda:{args.local_rank % ndev}"
                           if torch.cuda.is_available() else "cpu")

@@ -270,8 +270,22 @@ class BertModel(nn.Module):
 
 
 def _packed_cls(h, cu_seqlens):
-    """[B, H] first-token rows of a packed hidden stream h [1, T, H]."""
-    return h[0].index_select(0, cu_seqlens[:-1].long())
+    """[B, H] first-token rows of a packed hidden stream h [1, T, H]. An
+    empty sequence (``pack_batch(seq_multiple=...)``) starts at the total,
+    which is T when the stream is filled exactly: the clamp makes it gather
+    some finite row, which the loss ignores (label -100)."""
+    idx = cu_seqlens[:-1].long().clamp(max=h.shape[1] - 1)
+    return h[0].index_select(0, idx)
+
+
+def _cls_loss(logits, labels, cu_seqlens):
+    """Packed batches may carry empty sequences labelled -100; padded
+    batches take the plain mean."""
+    if labels is None:
+        return None
+    if cu_seqlens is not None:
+        return ops.cross_entropy(logits, labels, ignore_index=-100)
+    return ops.cross_entropy(logits, labels)
 
 
 def _checkpoint_layer(layer, h, mask, training, cpu_offload,
@@ -305,7 +319,7 @@ class BertForSequenceClassification(nn.Module):
                               cu_seqlens, max_seqlen, position_ids)
         pooled = ops.dropout(pooled, self.cfg.hidden_dropout_prob, self.training)
         logits = ops.linear(pooled, self.classifier.weight, self.classifier.bias)
-        loss = ops.cross_entropy(logits, labels) if labels is not None else None
+        loss = _cls_loss(logits, labels, cu_seqlens)
         return SequenceClassifierOutput(loss=loss, logits=logits)
 
     def gradient_checkpointing_enable(self, cpu_offload: bool = False):
@@ -349,7 +363,7 @@ class RobertaForSequenceClassification(nn.Module):
         x = ops.dropout(x, self.cfg.hidden_dropout_prob, self.training)
         logits = ops.linear(x, self.classifier.out_proj.weight,
                             self.classifier.out_proj.bias)
-        loss = ops.cross_entropy(logits, labels) if labels is not None else None
+        loss = _cls_loss(logits, labels, cu_seqlens)
         return SequenceClassifierOutput(loss=loss, logits=logits)
 
     def gradient_checkpointing_enable(self, cpu_offload: bool = False):

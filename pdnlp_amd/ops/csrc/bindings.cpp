@@ -61,6 +61,14 @@ std::vector<torch::Tensor> cross_entropy_fwd(torch::Tensor logits,
                                              torch::Tensor labels);
 torch::Tensor cross_entropy_bwd(torch::Tensor dloss, torch::Tensor logprobs,
                                 torch::Tensor labels);
+std::vector<torch::Tensor> cross_entropy_ignore_fwd(torch::Tensor logits,
+                                                    torch::Tensor labels,
+                                                    long ignore_index);
+torch::Tensor cross_entropy_ignore_bwd(torch::Tensor dloss,
+                                       torch::Tensor logprobs,
+                                       torch::Tensor labels,
+                                       torch::Tensor nvalid,
+                                       long ignore_index);
 void multi_tensor_adamw(std::vector<torch::Tensor> params,
                         std::vector<torch::Tensor> grads,
                         std::vector<torch::Tensor> exp_avgs,
@@ -136,6 +144,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         &bias_dropout_residual_ln_bwd_nodb);
   m.def("cross_entropy_fwd", &cross_entropy_fwd);
   m.def("cross_entropy_bwd", &cross_entropy_bwd);
+  m.def("cross_entropy_ignore_fwd", &cross_entropy_ignore_fwd);
+  m.def("cross_entropy_ignore_bwd", &cross_entropy_ignore_bwd);
   m.def("multi_tensor_adamw", &multi_tensor_adamw, py::arg("params"),
         py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"),
         py::arg("masters"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),

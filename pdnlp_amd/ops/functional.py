@@ -713,7 +713,39 @@ class _CrossEntropyFn(torch.autograd.Function):
         return ext().cross_entropy_bwd(dloss, logprobs, labels), None
 
 
-def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+class _CrossEntropyIgnoreFn(torch.autograd.Function):
+    """Mean over the rows whose label is not ``ignore_index``. The count of
+    those rows stays on the device (``nvalid``): no host sync, so the op can
+    be captured in a graph and replayed for any mix of valid/ignored rows."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index):
+        labels = labels.contiguous()
+        loss, logprobs, nvalid = ext().cross_entropy_ignore_fwd(
+            logits.contiguous(), labels, ignore_index)
+        ctx.save_for_backward(logprobs, labels, nvalid)
+        ctx.ignore_index = ignore_index
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logprobs, labels, nvalid = ctx.saved_tensors
+        return ext().cross_entropy_ignore_bwd(
+            dloss, logprobs, labels, nvalid, ctx.ignore_index), None, None
+
+
+def cross_entropy(logits: torch.Tensor, labels: torch.Tensor,
+                  ignore_index: Optional[int] = None) -> torch.Tensor:
+    """``ignore_index=None``: mean over all rows. Otherwise the semantics of
+    ``F.cross_entropy(..., ignore_index=...)``: mean over the rows whose
+    label differs from it (at least one such row is a precondition), zero
+    gradient for the others."""
+    if ignore_index is None:
+        if hip_enabled(logits):
+            return _CrossEntropyFn.apply(logits.float(), labels)
+        return F.cross_entropy(logits.float(), labels)
     if hip_enabled(logits):
-        return _CrossEntropyFn.apply(logits.float(), labels)
-    return F.cross_entropy(logits.float(), labels)
+        return _CrossEntropyIgnoreFn.apply(logits.float(), labels,
+                                           int(ignore_index))
+    return F.cross_entropy(logits.float(), labels,
+                           ignore_index=int(ignore_index))
