@@ -18,6 +18,8 @@
 #include <ATen/hip/HIPContext.h>
 
 #include <cstdlib>
+#include <mutex>
+#include <unordered_map>
 
 #include "gemm_common.h"
 
@@ -182,11 +184,19 @@ void gemm_tn_w8_kernel(const T* __restrict__ A, const T* __restrict__ B,
 // wave issues 9 MFMAs per ms step instead of 8. The fp32 slices land behind
 // the dW partials, P[sm*N*K + split*N + n], without atomics. The dW
 // accumulators are untouched, so C is bit-identical to the plain kernel's.
-template <typename T, typename V8, bool RAWBAR, bool COLSUM>
+//
+// FOLD: no second launch. Each workgroup stores its fp32 slab, publishes it
+// and takes a ticket on its tile's counter; the workgroup that draws the
+// tile's last ticket folds the sm slabs in slice order (the add order of
+// fold_partials4, so C and CS are bit-identical to the two-launch path's)
+// and writes the C tile. See "in-launch fold" below the main loop.
+template <typename T, typename V8, bool RAWBAR, bool COLSUM, bool FOLD>
 __global__ __launch_bounds__(512)
 void gemm_tn_sk_kernel(const T* __restrict__ A, const T* __restrict__ B,
-                       float* __restrict__ P, long M, long N, long K,
-                       int tiles_k, int ntiles, int sm, int nwg) {
+                       float* __restrict__ P, T* __restrict__ C,
+                       T* __restrict__ CS, unsigned int* __restrict__ cnt,
+                       long M, long N, long K, int tiles_k, int ntiles,
+                       int sm, int nwg) {
   constexpr int BTN = 128, BTK = 128;
   constexpr int GLDS = 4;  // stage_tr wave-instructions per buffer
   const int wg = xcd_remap(blockIdx.x, nwg);
@@ -301,30 +311,144 @@ void gemm_tn_sk_kernel(const T* __restrict__ A, const T* __restrict__ B,
     cur ^= 1;
   }
 
-  float* Pout = P + (long)split * N * K;
   const int crow_off = (lane >> 4) * 4;
   const int ccol = lane & 15;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const long k = k0 + wc + j * 16 + ccol;
-      if (k >= K) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long n = n0 + wr + i * 16 + crow_off + r;
-        if (n >= N) continue;
-        Pout[n * K + k] = acc[i][j][r];
-      }
-    }
-  }
   if constexpr (COLSUM) {
     if (do_cs && ccol == 0) {
       float* PS = P + (long)sm * N * K + (long)split * N;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const long n = n0 + wr + cs_q * 16 + crow_off + r;
-        if (n < N) PS[n] = cs_acc[r];
+        if (n >= N) continue;
+        if constexpr (FOLD)  // handed to the folding workgroup: sc1 store
+          __hip_atomic_store(PS + n, cs_acc[r], __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+        else
+          PS[n] = cs_acc[r];
+      }
+    }
+  }
+  if constexpr (!FOLD) {
+    float* Pout = P + (long)split * N * K;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const long k = k0 + wc + j * 16 + ccol;
+        if (k >= K) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const long n = n0 + wr + i * 16 + crow_off + r;
+          if (n >= N) continue;
+          Pout[n * K + k] = acc[i][j][r];
+        }
+      }
+    }
+  } else {
+    // ---- in-launch fold ----------------------------------------------------
+    // Slabs are private workspace in fragment order: slab (split, tile) is
+    // [wave][i][j][lane] f32x4, so one wave-instruction stores 1 KiB
+    // contiguous in 16-byte lanes (the host only takes this path on the full
+    // 128 grid, so no bounds here).
+    //
+    // Hand-off without fences: every slab byte is stored write-through
+    // (sc1, 16 B per lane) and drained by its wave before one lane takes
+    // the tile's ticket, and every slab load of the folding workgroup is an
+    // sc1 load, which no CU's L1 serves. Plain stores behind an agent-scope
+    // release cost the launch more than the fold launch they replace: the
+    // release writes the XCD's L2 back once per workgroup.
+    constexpr long SLAB = (long)BTN * BTK;
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const int foff = (wid * 8 * WAVE + lane) * 16;  // bytes into a slab
+    auto slab_rsrc = [&](int s) {  // wave-uniform descriptor of one slab
+      return __builtin_amdgcn_make_buffer_rsrc(
+          P + ((long)s * ntiles + tile) * SLAB, 0, (int)(SLAB * 4),
+          0x00020000);
+    };
+    {
+      const auto rs = slab_rsrc(split);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          __builtin_amdgcn_raw_buffer_store_b128(
+              reinterpret_cast<const u32x4&>(acc[i][j]), rs,
+              foff + (i * 2 + j) * WAVE * 16, 0, /*sc1*/ 16);
+      }
+    }
+    // publish: every wave drains its stores, then one lane takes the
+    // ticket. The counter wraps to 0 with the last ticket (atomic inc with
+    // bound sm - 1), so it is back at 0 for the next launch whatever that
+    // launch's sm is, with no reset and no epoch.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    // the staging LDS is idle from here on: its first word carries the
+    // ticket to the other waves (no further __shared__ object)
+    unsigned int* lds_ticket = reinterpret_cast<unsigned int*>(&lds_b[0][0]);
+    if (threadIdx.x == 0)
+      *lds_ticket = __builtin_amdgcn_atomic_inc32(
+          cnt + tile, (unsigned int)(sm - 1), __ATOMIC_RELAXED, "agent");
+    __syncthreads();
+    if (*lds_ticket != (unsigned int)(sm - 1)) return;  // not last: done
+
+    // last arriver: all sm slabs of the tile are in memory. Its own slab is
+    // still in registers and takes its place in the slice order from there
+    // (the same bits, 64 KB less to read); the branch is wave-uniform and
+    // around all eight loads of a slab, not one per load.
+    auto get_slab = [&](int s, f32x4 (&v)[8]) {
+      if (s == split) {
+#pragma unroll
+        for (int f = 0; f < 8; ++f) v[f] = acc[f >> 1][f & 1];
+      } else {
+        const auto rs = slab_rsrc(s);
+#pragma unroll
+        for (int f = 0; f < 8; ++f) {
+          const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(
+              rs, foff + f * WAVE * 16, 0, /*sc1*/ 16);
+          v[f] = reinterpret_cast<const f32x4&>(x);
+        }
+      }
+    };
+    f32x4 sum[8];
+    get_slab(0, sum);
+    for (int s = 1; s < sm; ++s) {
+      f32x4 v[8];
+      get_slab(s, v);
+#pragma unroll
+      for (int f = 0; f < 8; ++f) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) sum[f][q] += v[f][q];
+      }
+    }
+    // through the staging LDS as a [128][128] tile of T, then full rows out
+    T* lds_c = reinterpret_cast<T*>(&lds_a[0][0]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          lds_c[(wr + i * 16 + crow_off + r) * BTK + wc + j * 16 + ccol] =
+              from_f32<T>(sum[i * 2 + j][r]);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const int q = it * 512 + threadIdx.x;  // 16-byte piece of the tile
+      const int row = q >> 4, c8 = (q & 15) * 8;
+      *reinterpret_cast<u32x4*>(C + (n0 + row) * K + k0 + c8) =
+          *reinterpret_cast<const u32x4*>(lds_c + row * BTK + c8);
+    }
+    if constexpr (COLSUM) {
+      if (do_cs && threadIdx.x < BTN) {
+        const float* PS = P + (long)sm * N * K + n0 + threadIdx.x;
+        float a = __hip_atomic_load(PS, __ATOMIC_RELAXED,
+                                    __HIP_MEMORY_SCOPE_AGENT);
+        for (int s = 1; s < sm; ++s)
+          a += __hip_atomic_load(PS + (long)s * N, __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT);
+        CS[n0 + threadIdx.x] = from_f32<T>(a);
       }
     }
   }
@@ -393,26 +517,79 @@ bool tn_v2_ok(long N, long K) {
   return getenv("PDNLP_TN_V1") == nullptr && N % 128 == 0 && K % 128 == 0;
 }
 
-// v2 launches: gemm_tn_sk_kernel into the partials P, then the fold into C
-// (and CS when `colsum`). `sync` picks the vmcnt(0)+__syncthreads schedule
-// over the raw-barrier counted-vmcnt one.
+// ---- per-tile ticket counters of the in-launch fold -------------------------
+// One persistent zeroed buffer per device, TN_CNT_SLOTS regions of
+// TN_CNT_TILES counters; every stream that launches the fold gets a region of
+// its own, so launches that can overlap never share a counter, and launches
+// on one stream are ordered. A counter returns to 0 with its tile's last
+// ticket (see the kernel), so nothing is reset per call, the same counters
+// serve any sm in turn, and a replayed graph finds them as a first launch
+// does. The buffer is made on the first eager call; a capture that comes
+// before it, a 17th stream or more tiles than a region holds get nullptr and
+// take the two-launch path. A launch that dies midway leaves counters
+// unbalanced, as it leaves everything else on its device.
+constexpr int TN_CNT_TILES = 4096;
+constexpr int TN_CNT_SLOTS = 16;
+
+struct TnCounters {
+  torch::Tensor buf;
+  std::unordered_map<hipStream_t, int> slot;
+};
+
+unsigned int* tn_fold_counters(const torch::Tensor& like, hipStream_t stream,
+                               int tiles2) {
+  if (tiles2 > TN_CNT_TILES) return nullptr;
+  static std::mutex mu;
+  static auto* pool = new std::unordered_map<int, TnCounters>();  // leaked
+  std::lock_guard<std::mutex> lock(mu);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  HIP_CHECK(hipStreamIsCapturing(stream, &cap));
+  const int dev = like.get_device();
+  auto it = pool->find(dev);
+  if (it == pool->end()) {
+    if (cap != hipStreamCaptureStatusNone) return nullptr;
+    TnCounters c;
+    c.buf = torch::zeros({(long)TN_CNT_SLOTS * TN_CNT_TILES},
+                         like.options().dtype(torch::kInt32));
+    // the fill runs on this stream; other streams' regions must see it too
+    HIP_CHECK(hipStreamSynchronize(stream));
+    it = pool->emplace(dev, std::move(c)).first;
+  }
+  auto& c = it->second;
+  auto st = c.slot.find(stream);
+  if (st == c.slot.end()) {
+    if ((int)c.slot.size() >= TN_CNT_SLOTS) return nullptr;
+    st = c.slot.emplace(stream, (int)c.slot.size()).first;
+  }
+  return reinterpret_cast<unsigned int*>(c.buf.data_ptr<int>()) +
+         (long)st->second * TN_CNT_TILES;
+}
+
+// v2 launches: gemm_tn_sk_kernel, which folds its own partials into C (and
+// CS when `colsum`) when it gets ticket counters `cnt`, else writes them to
+// P for the fold launch behind it. `sync` picks the vmcnt(0)+__syncthreads
+// schedule over the raw-barrier counted-vmcnt one.
 template <typename T, typename V8>
 void launch_tn_v2(const torch::Tensor& A, const torch::Tensor& B,
                   torch::Tensor& P, torch::Tensor& C, torch::Tensor& CS,
                   long M, long N, long K, int tiles2, int sm, bool colsum,
-                  bool sync, hipStream_t stream) {
+                  bool sync, unsigned int* cnt, hipStream_t stream) {
   const int nwg2 = tiles2 * sm;
   const long NK = N * K;
   const int rblocks = (int)((NK / 4 + 255) / 256);
-  auto kernel =
-      colsum ? (sync ? gemm_tn_sk_kernel<T, V8, false, true>
-                     : gemm_tn_sk_kernel<T, V8, true, true>)
-             : (sync ? gemm_tn_sk_kernel<T, V8, false, false>
-                     : gemm_tn_sk_kernel<T, V8, true, false>);
-  hipLaunchKernelGGL(kernel, dim3(nwg2), dim3(512), 0, stream,
-                     (const T*)A.data_ptr(), (const T*)B.data_ptr(),
-                     (float*)P.data_ptr(), M, N, K, (int)(K / 128), tiles2,
-                     sm, nwg2);
+  DISPATCH_BOOL(cnt != nullptr, FOLD, [&] {
+    auto kernel =
+        colsum ? (sync ? gemm_tn_sk_kernel<T, V8, false, true, FOLD>
+                       : gemm_tn_sk_kernel<T, V8, true, true, FOLD>)
+               : (sync ? gemm_tn_sk_kernel<T, V8, false, false, FOLD>
+                       : gemm_tn_sk_kernel<T, V8, true, false, FOLD>);
+    hipLaunchKernelGGL(kernel, dim3(nwg2), dim3(512), 0, stream,
+                       (const T*)A.data_ptr(), (const T*)B.data_ptr(),
+                       (float*)P.data_ptr(), (T*)C.data_ptr(),
+                       colsum ? (T*)CS.data_ptr() : nullptr, cnt, M, N, K,
+                       (int)(K / 128), tiles2, sm, nwg2);
+  });
+  if (cnt != nullptr) return;
   if (colsum) {
     const int cblocks = (int)((N / 4 + 255) / 256);
     hipLaunchKernelGGL((reduce_partials_colsum_kernel<T>),
@@ -483,12 +660,17 @@ std::pair<torch::Tensor, torch::Tensor> tn_impl(const torch::Tensor& A,
   // measured on two boxes), PDNLP_TN_SYNC reverts — except that plain fp16
   // has only ever run the synchronous one (open inconsistency)
   const bool sync = getenv("PDNLP_TN_SYNC") != nullptr || (!colsum && !bf16);
+  // the fold runs inside the GEMM launch; PDNLP_TN_FOLD2 keeps the separate
+  // fold launch (the A/B baseline and the reference of the bit-identity test)
+  unsigned int* cnt = getenv("PDNLP_TN_FOLD2") != nullptr
+                          ? nullptr
+                          : tn_fold_counters(A, stream, tiles2);
   if (bf16)
     launch_tn_v2<__hip_bfloat16, bf16x8>(A, B, P, C, CS, M, N, K, tiles2, sm,
-                                         colsum, sync, stream);
+                                         colsum, sync, cnt, stream);
   else
     launch_tn_v2<__half, f16x8>(A, B, P, C, CS, M, N, K, tiles2, sm, colsum,
-                                sync, stream);
+                                sync, cnt, stream);
   return {C, CS};
 }
 
