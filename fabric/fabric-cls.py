@@ -48,6 +48,10 @@ def main():
         raise SystemExit("--max-tokens is not supported by this entrypoint "
                          "(its own loop feeds padded [B, S] batches); use "
                          "single-gpu-cls.py or a multi-gpu-*-cls.py script")
+    if args.attn_tile_pack:
+        raise SystemExit("--attn-tile-pack is not supported by this "
+                         "entrypoint (it needs --unpad true); use "
+                         "single-gpu-cls.py or a multi-gpu-*-cls.py script")
     if args.unpad:
         raise SystemExit("--unpad true is not supported by this entrypoint "
                          "(its own loop feeds padded [B, S] batches); use "

@@ -56,6 +56,7 @@ def main():
     model = build_model(base.model, model_path=base.model_path)
     hf_args.unpad = base.unpad
     hf_args.max_tokens = base.max_tokens
+    hf_args.attn_tile_pack = base.attn_tile_pack
     trainer = HFStyleTrainer(model, hf_args, train_dataset=train_ds,
                              eval_dataset=dev_ds, data_collator=collate,
                              compute_metrics=compute_metrics)

@@ -22,7 +22,8 @@ from .data import (SEQ_MULTIPLE, ClsDataset, Collate, DistributedSampler,
                    LABELS, SyntheticClsDataset, TokenBudgetBatchSampler,
                    build_tokenizer, load_data, sequence_lengths,
                    train_dev_split)
-from .engine.trainer import build_training, check_token_budget
+from .engine.trainer import (build_training, check_attn_tile_pack,
+                             check_token_budget)
 from .parallel.bootstrap import cleanup, init_distributed, spawn
 from .utils import set_seed
 from .utils.checkpoint import load_checkpoint
@@ -65,6 +66,7 @@ def token_budget_loader(args: Args, dataset, collate: Collate,
 
 def build_dataloaders(args: Args, world_size: int, rank: int):
     check_token_budget(args)
+    check_attn_tile_pack(args)
     vocab_size = _VOCAB.get(getattr(args, "model", "bert-base"), 21128)
     if os.path.isfile(args.data_path):
         data = load_data(args.data_path, limit=args.data_limit)

@@ -33,6 +33,8 @@ class BertConfig:
     num_labels: int = 6                # 6 emotion classes (reference data/train.json)
     pad_token_id: int = 0
     model_type: str = "bert"           # "bert" | "roberta"
+    attn_tile_pack: bool = False       # packed batches: several short
+                                       # sequences per 64-row attention tile
 
     @property
     def head_dim(self) -> int:
@@ -115,6 +117,9 @@ class Args:
                                        # train_batch_size sentences (0 = off)
     max_sentences: int = 0             # cap on sentences per budgeted batch
                                        # (0 = none)
+    attn_tile_pack: bool = False       # with unpad: tile-packed attention,
+                                       # several whole short sequences per
+                                       # 64-row tile (models' attn_tile_pack)
 
     # optimization
     train_batch_size: int = 32         # per GPU

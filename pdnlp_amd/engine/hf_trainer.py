@@ -49,6 +49,7 @@ class TrainingArguments:
     max_tokens: int = 0   # with unpad: token-budget train batches of this
                           # many packed rows (per_device_train_batch_size
                           # is then not used); 0 = off
+    attn_tile_pack: bool = False  # with unpad: tile-packed attention
     # global-norm gradient clipping, 0 = off. HF's own default is 1.0 (so
     # the reference's transformers run clips); set 1.0 to reproduce it.
     max_grad_norm: float = 0.0
@@ -81,6 +82,7 @@ class HFStyleTrainer:
         eargs.seed = args.seed
         eargs.unpad = args.unpad
         eargs.max_tokens = args.max_tokens
+        eargs.attn_tile_pack = args.attn_tile_pack
         eargs.max_grad_norm = args.max_grad_norm
         eargs.output_dir = args.output_dir
         eargs.ckpt_path = os.path.join(args.output_dir, "best_model.pt")

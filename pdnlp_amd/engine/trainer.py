@@ -144,6 +144,7 @@ class Trainer:
         # optional per-step hook: fn(trainer) called after every global step
         # (HFStyleTrainer uses it for checkpoint-N dirs)
         self.step_callback = None
+        apply_attn_tile_pack(args, model)
 
     # ------------------------------------------------------------------
     def on_step(self, batch):
@@ -703,6 +704,30 @@ def check_token_budget(args) -> None:
                 f"row granule of the packed stream.")
 
 
+def check_attn_tile_pack(args) -> None:
+    """Reject ``--attn-tile-pack true`` without the packed stream."""
+    if getattr(args, "attn_tile_pack", False) \
+            and not getattr(args, "unpad", False):
+        raise ValueError(
+            "--attn-tile-pack needs --unpad true: it packs the short "
+            "sequences of the packed stream into shared attention tiles, "
+            "which padded [B, S] batches do not have.")
+
+
+def apply_attn_tile_pack(args, model) -> None:
+    """Hand ``args.attn_tile_pack`` to the (unwrapped) model's config. The
+    model builds the tile plan itself, once per forward, so nothing else in
+    the step (batch dict, graph key, strategy wrappers) knows about it."""
+    check_attn_tile_pack(args)
+    if getattr(args, "attn_tile_pack", False):
+        inner = getattr(model, "module", model)
+        cfg = getattr(inner, "cfg", None)
+        if cfg is None or not hasattr(cfg, "attn_tile_pack"):
+            raise ValueError("--attn-tile-pack: the model has no "
+                             "attn_tile_pack config field")
+        cfg.attn_tile_pack = True
+
+
 def build_training(args, model=None, label_key: str = "label"):
     """Assemble (model, optimizer, scaler, trainer) for a strategy mode.
 
@@ -724,6 +749,7 @@ def build_training(args, model=None, label_key: str = "label"):
             "DataParallel splits the batch on dim 0, which a packed token "
             "stream does not have. Use strategy=ddp (one process per GPU).")
     check_token_budget(args)
+    check_attn_tile_pack(args)
     ndev = max(torch.cuda.device_count(), 1)
     device = torch.device(f"cuda:{args.local_rank % ndev}"
                           if torch.cuda.is_available() else "cpu")

@@ -158,7 +158,8 @@ class BertLayer(nn.Module):
 
     def forward(self, h: torch.Tensor, attn_mask: Optional[torch.Tensor],
                 training: bool, cu_seqlens: Optional[torch.Tensor] = None,
-                max_seqlen: Optional[int] = None) -> torch.Tensor:
+                max_seqlen: Optional[int] = None,
+                attn_plan=None) -> torch.Tensor:
         cfg = self.cfg
         nh = cfg.num_attention_heads
         a = self.attention.self
@@ -172,7 +173,8 @@ class BertLayer(nn.Module):
             # packed stream h [1, T, H]: sequence-boundary-aware attention
             ctx = ops.attention_varlen(
                 qkv[0], cu_seqlens, max_seqlen, nh,
-                cfg.attention_probs_dropout_prob, training).unsqueeze(0)
+                cfg.attention_probs_dropout_prob, training,
+                plan=attn_plan).unsqueeze(0)
         else:
             ctx = ops.attention_packed(
                 qkv, attn_mask, nh, cfg.attention_probs_dropout_prob,
@@ -226,6 +228,7 @@ class BertModel(nn.Module):
         ``attention_mask`` is ignored, and the hidden states come back as
         the packed [1, T, H] stream."""
         training = self.training
+        attn_plan = None
         if cu_seqlens is not None:
             assert input_ids.dim() == 1 and position_ids is not None \
                 and max_seqlen is not None, \
@@ -235,6 +238,11 @@ class BertModel(nn.Module):
             h = self.embeddings(input_ids.unsqueeze(0), tt, training,
                                 position_ids.unsqueeze(0))
             addmask = None
+            # tile-packed attention: one plan per forward, shared by every
+            # layer; a function of the contents of cu_seqlens alone
+            if self.cfg.attn_tile_pack:
+                attn_plan = ops.varlen_attention_plan(cu_seqlens,
+                                                      input_ids.numel())
         else:
             if attention_mask is None:
                 attention_mask = torch.ones_like(input_ids)
@@ -248,9 +256,10 @@ class BertModel(nn.Module):
             if self._grad_ckpt and training:
                 h = _checkpoint_layer(layer, h, addmask, training,
                                       self._ckpt_cpu_offload, cu_seqlens,
-                                      max_seqlen)
+                                      max_seqlen, attn_plan)
             else:
-                h = layer(h, addmask, training, cu_seqlens, max_seqlen)
+                h = layer(h, addmask, training, cu_seqlens, max_seqlen,
+                          attn_plan)
         if cu_seqlens is not None:
             cls = _packed_cls(h, cu_seqlens)
         else:
@@ -289,7 +298,7 @@ def _cls_loss(logits, labels, cu_seqlens):
 
 
 def _checkpoint_layer(layer, h, mask, training, cpu_offload,
-                      cu_seqlens=None, max_seqlen=None):
+                      cu_seqlens=None, max_seqlen=None, attn_plan=None):
     """Activation checkpointing (deepspeed-capability equivalent,
     reference config: multi-gpu-deepspeed-cls.py:240-244), optional CPU
     offload of the saved input over PCIe."""
@@ -298,9 +307,9 @@ def _checkpoint_layer(layer, h, mask, training, cpu_offload,
         ctx = torch.autograd.graph.save_on_cpu(pin_memory=True)
         with ctx:
             return cp.checkpoint(layer, h, mask, training, cu_seqlens,
-                                 max_seqlen, use_reentrant=False)
+                                 max_seqlen, attn_plan, use_reentrant=False)
     return cp.checkpoint(layer, h, mask, training, cu_seqlens, max_seqlen,
-                         use_reentrant=False)
+                         attn_plan, use_reentrant=False)
 
 
 class BertForSequenceClassification(nn.Module):

@@ -80,6 +80,7 @@ from .functional import (  # noqa: F401,E402
     attention,
     attention_packed,
     attention_varlen,
+    varlen_attention_plan,
     masked_softmax,
     cross_entropy,
     bias_dropout_residual_layernorm,
@@ -87,6 +88,11 @@ from .functional import (  # noqa: F401,E402
     dropout,
     reseed_dropout,
     dw_stream_join,
+)
+from .tile_plan import (  # noqa: F401,E402
+    AttnTilePlan,
+    tile_plan_max_items,
+    tile_plan_reference,
 )
 from .adamw import FusedAdamW, multi_tensor_adamw  # noqa: F401,E402
 from .grad_clip import (  # noqa: F401,E402

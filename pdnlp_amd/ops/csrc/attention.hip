@@ -30,6 +30,12 @@
 // rows are never stored, so the zero-filled outputs stay exactly zero
 // outside the sequences.
 //
+// TP (tile-packed) instantiations are VARLEN kernels whose blocks come from
+// a device-built tile plan: one 64-row tile may hold several whole
+// consecutive short sequences, and scores between them are masked inside
+// the tile (see TP_COUNT below and fa_tile_plan_kernel). Opt-in; the other
+// instantiations do not change.
+//
 // LDS image convention: every tile is a gfx950 "tr-image" (see tr_addr
 // below) that serves both normal and hardware-transposed fragment reads
 // from the same staging.
@@ -175,12 +181,45 @@ __device__ __forceinline__ int varlen_len(const int* cu_seqlens, long b,
   return (int)(len < cap ? len : cap);
 }
 
+// Tile-packed (TP) instantiations: the VARLEN kernels over a tile plan (see
+// fa_tile_plan_kernel) instead of over (sequence, tile) pairs. The plan is
+// one int32 buffer that rides in the cu_seqlens argument: the item count at
+// [TP_COUNT], gridDim.x items {first packed row, row count, tile, 0} from
+// TP_ITEMS on, then {start, end} of every packed row's sequence. A block
+// takes (row0, len, tile) from item blockIdx.x; an item of at most 64 rows
+// is a group of whole consecutive sequences that share one tile, and a score
+// is live only where the key lies inside the query row's own sequence.
+constexpr int TP_COUNT = 0;
+constexpr int TP_ITEMS = 4;
+
+// TP prologue: {start, end} - row0 of the 64 rows of tile `tile` into LDS
+// (ordinary loads, before the KV loop). Rows past the item's end hold
+// clamped copies and are never stored: they get the item's own span, which
+// keeps their scores finite as in the VARLEN kernels.
+__device__ __forceinline__ void tp_stage_bounds(const int* plan, long row0,
+                                                int len, long tile,
+                                                int* bnd_lds) {
+  if (threadIdx.x < 64) {
+    const long g = tile * 64 + threadIdx.x;
+    int lo = 0, hi = len;
+    if (g < len) {
+      const int* bp = plan + TP_ITEMS + 4 * (long)gridDim.x + 2 * (row0 + g);
+      lo = bp[0] - (int)row0;
+      hi = bp[1] - (int)row0;
+      lo = lo > 0 ? lo : 0;
+      hi = hi < len ? hi : len;
+    }
+    bnd_lds[2 * threadIdx.x] = lo;
+    bnd_lds[2 * threadIdx.x + 1] = hi;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
 
 template <typename T, typename V8, bool HAS_MASK, bool DROP, bool PRELOAD,
-          bool VARLEN>
+          bool VARLEN, bool TP>
 __global__ __launch_bounds__(NTHREADS)
 void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
                    T* __restrict__ o, float* __restrict__ lse,
@@ -189,12 +228,17 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
                    int nh, int S, const int* __restrict__ cu_seqlens) {
   scale *= 1.4426950408889634f;  // exp2 domain (log2 e)
   const int bh = blockIdx.y;
-  const long b = bh / nh, h = bh % nh;
-  const long rb = blockIdx.x;
+  const long b = TP ? 0 : bh / nh, h = TP ? bh : bh % nh;
+  // TP: cu_seqlens carries the tile plan, blockIdx.x an item of it
+  if (TP && (int)blockIdx.x >= cu_seqlens[TP_COUNT]) return;  // block-uniform
+  const int* item =
+      TP ? cu_seqlens + TP_ITEMS + 4 * (long)blockIdx.x : nullptr;
+  const long rb = TP ? (long)item[2] : (long)blockIdx.x;
   const long H = (long)nh * 64, ld = 3 * H;
   // the block's sequence is rows [row0, row0 + len); VARLEN: S carries T
-  const long row0 = VARLEN ? (long)cu_seqlens[b] : b * S;
-  const int len = VARLEN ? varlen_len(cu_seqlens, b, row0, S) : S;
+  const long row0 = TP ? (long)item[0] : VARLEN ? (long)cu_seqlens[b] : b * S;
+  const int len = TP ? item[1]
+                     : VARLEN ? varlen_len(cu_seqlens, b, row0, S) : S;
   if (VARLEN && rb * 64 >= len) return;  // block-uniform, before any barrier
   const long stat0 = VARLEN ? h * S + row0 : (long)bh * S;  // lse row base
   const T* qbase = qkv + row0 * ld + h * 64;
@@ -230,6 +274,12 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
   if (HAS_MASK)
     for (int i = threadIdx.x; i < S; i += NTHREADS)
       mask_lds[i] = mask[b * S + i];
+  int* bnd_lds = nullptr;
+  if constexpr (TP) {
+    __shared__ int bnd_s[128];
+    bnd_lds = bnd_s;
+    tp_stage_bounds(cu_seqlens, row0, len, rb, bnd_lds);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -237,6 +287,15 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
   f32x4 acc_o[4] = {};
 #pragma unroll
   for (int r = 0; r < 4; ++r) { m[r] = -INFINITY; l[r] = 0.f; }
+  // TP: live keys of this lane's four query rows, [klo, khi) relative to row0
+  int klo[4] = {}, khi[4] = {};
+  if constexpr (TP) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      klo[r] = bnd_lds[2 * (wr + (lane >> 4) * 4 + r)];
+      khi[r] = bnd_lds[2 * (wr + (lane >> 4) * 4 + r) + 1];
+    }
+  }
 
   const int nt = VARLEN ? (len + 63) / 64 : S / 64;
   int cur = 0;
@@ -271,7 +330,13 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
         // keys past the sequence end (the staged rows there are clamped
         // copies): score -inf, so P is exactly 0. Tile t always holds at
         // least one real key, which keeps the running max finite.
-        if (VARLEN && t * 64 + j * 16 + (lane & 15) >= len)
+        // TP: also keys of the tile's other sequences. A real row of a
+        // group has itself as a key in the group's only tile, a row of a
+        // long sequence has a key in every tile as above, and rows past
+        // the item's end see its whole span: the running max stays finite.
+        if (TP ? (t * 64 + j * 16 + (lane & 15) < klo[r] ||
+                  t * 64 + j * 16 + (lane & 15) >= khi[r])
+               : (VARLEN && t * 64 + j * 16 + (lane & 15) >= len))
           s[j][r] = -INFINITY;
         x = fmaxf(x, s[j][r]);
       }
@@ -300,8 +365,11 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
         const int kcol = j * 16 + (lane & 15);
         float pv = s[j][r];
         if (DROP) {
+          // TP: key index inside the row's own sequence, so the masks are
+          // those of the per-sequence kernels
           const unsigned int rr = hash_rng32(
-              seed32, drop_idx<VARLEN>(grow, t * 64 + kcol, S));
+              seed32, drop_idx<VARLEN>(
+                          grow, t * 64 + kcol - (TP ? klo[r] : 0), S));
           pv = (rr * 2.3283064365386963e-10f) >= p ? pv * inv_keep : 0.f;
         }
         *reinterpret_cast<unsigned short*>(
@@ -349,7 +417,7 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
 // ---------------------------------------------------------------------------
 
 template <typename T, typename V8, bool HAS_MASK, bool DROP, bool PRELOAD,
-          bool VARLEN>
+          bool VARLEN, bool TP>
 __global__ __launch_bounds__(NTHREADS)
 void fa_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
                       const T* __restrict__ o, const float* __restrict__ lse,
@@ -360,12 +428,17 @@ void fa_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
                       int nh, int S, const int* __restrict__ cu_seqlens) {
   const float scale2 = scale * 1.4426950408889634f;  // exp2 domain
   const int bh = blockIdx.y;
-  const long b = bh / nh, h = bh % nh;
-  const long rb = blockIdx.x;
+  const long b = TP ? 0 : bh / nh, h = TP ? bh : bh % nh;
+  // TP: cu_seqlens carries the tile plan, blockIdx.x an item of it
+  if (TP && (int)blockIdx.x >= cu_seqlens[TP_COUNT]) return;  // block-uniform
+  const int* item =
+      TP ? cu_seqlens + TP_ITEMS + 4 * (long)blockIdx.x : nullptr;
+  const long rb = TP ? (long)item[2] : (long)blockIdx.x;
   const long H = (long)nh * 64, ld = 3 * H;
   // sequence rows [row0, row0 + len), as in fa_fwd_kernel
-  const long row0 = VARLEN ? (long)cu_seqlens[b] : b * S;
-  const int len = VARLEN ? varlen_len(cu_seqlens, b, row0, S) : S;
+  const long row0 = TP ? (long)item[0] : VARLEN ? (long)cu_seqlens[b] : b * S;
+  const int len = TP ? item[1]
+                     : VARLEN ? varlen_len(cu_seqlens, b, row0, S) : S;
   if (VARLEN && rb * 64 >= len) return;  // block-uniform, before any barrier
   const long stat0 = VARLEN ? h * S + row0 : (long)bh * S;  // lse/dvec base
   const T* qbase = qkv + row0 * ld + h * 64;
@@ -404,9 +477,24 @@ void fa_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
   if (HAS_MASK)
     for (int i = threadIdx.x; i < S; i += NTHREADS)
       mask_lds[i] = mask[b * S + i];
+  int* bnd_lds = nullptr;
+  if constexpr (TP) {
+    __shared__ int bnd_s[128];
+    bnd_lds = bnd_s;
+    tp_stage_bounds(cu_seqlens, row0, len, rb, bnd_lds);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
+  // TP: live keys of this lane's four query rows, as in fa_fwd_kernel
+  int klo[4] = {}, khi[4] = {};
+  if constexpr (TP) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      klo[r] = bnd_lds[2 * (wr + (lane >> 4) * 4 + r)];
+      khi[r] = bnd_lds[2 * (wr + (lane >> 4) * 4 + r) + 1];
+    }
+  }
   {
     // lane l&15 accumulates row wr+(l&15) over its quarter's 8 columns
     float acc = 0.f;
@@ -487,13 +575,17 @@ void fa_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
         float dp = acc_dp[j][r];
         if (DROP) {
           const unsigned int rr = hash_rng32(
-              seed32, drop_idx<VARLEN>(grow, t * 64 + kcol, S));
+              seed32, drop_idx<VARLEN>(
+                          grow, t * 64 + kcol - (TP ? klo[r] : 0), S));
           dp = (rr * 2.3283064365386963e-10f) >= p ? dp * inv_keep : 0.f;
         }
         float dsv = pv * (dp - dvec_r[r]) * scale;
         // tail keys and tail query rows: dS is 0 by index (pv there comes
-        // from clamped copies, not from data)
-        if (VARLEN && (t * 64 + kcol >= len || rb * 64 + prow >= len))
+        // from clamped copies, not from data). TP: keys of another
+        // sequence too, where exp2(s - lse) may have overflowed.
+        if (TP ? (t * 64 + kcol < klo[r] || t * 64 + kcol >= khi[r] ||
+                  rb * 64 + prow >= len)
+               : (VARLEN && (t * 64 + kcol >= len || rb * 64 + prow >= len)))
           dsv = 0.f;
         *reinterpret_cast<unsigned short*>(
             ds_lds + tr_addr(prow, kcol)) =
@@ -536,7 +628,7 @@ void fa_bwd_dq_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
 // ---------------------------------------------------------------------------
 
 template <typename T, typename V8, bool HAS_MASK, bool DROP, bool PRELOAD,
-          bool VARLEN>
+          bool VARLEN, bool TP>
 __global__ __launch_bounds__(NTHREADS)
 void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
                        const T* __restrict__ /*o: consumed by the dQ pass*/,
@@ -548,12 +640,17 @@ void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
                        int nh, int S, const int* __restrict__ cu_seqlens) {
   const float scale2 = scale * 1.4426950408889634f;  // exp2 domain
   const int bh = blockIdx.y;
-  const long b = bh / nh, h = bh % nh;
-  const long kb = blockIdx.x;
+  const long b = TP ? 0 : bh / nh, h = TP ? bh : bh % nh;
+  // TP: cu_seqlens carries the tile plan, blockIdx.x an item of it
+  if (TP && (int)blockIdx.x >= cu_seqlens[TP_COUNT]) return;  // block-uniform
+  const int* item =
+      TP ? cu_seqlens + TP_ITEMS + 4 * (long)blockIdx.x : nullptr;
+  const long kb = TP ? (long)item[2] : (long)blockIdx.x;
   const long H = (long)nh * 64, ld = 3 * H;
   // sequence rows [row0, row0 + len), as in fa_fwd_kernel
-  const long row0 = VARLEN ? (long)cu_seqlens[b] : b * S;
-  const int len = VARLEN ? varlen_len(cu_seqlens, b, row0, S) : S;
+  const long row0 = TP ? (long)item[0] : VARLEN ? (long)cu_seqlens[b] : b * S;
+  const int len = TP ? item[1]
+                     : VARLEN ? varlen_len(cu_seqlens, b, row0, S) : S;
   if (VARLEN && kb * 64 >= len) return;  // block-uniform, before any barrier
   const long stat0 = VARLEN ? h * S + row0 : (long)bh * S;  // lse/dvec base
   const T* qbase = qkv + row0 * ld + h * 64;
@@ -593,8 +690,25 @@ void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
     lse_lds[i] = lse[stat0 + i];
     dvec_lds[i] = dvec[stat0 + i];
   }
+  int* bnd_lds = nullptr;
+  if constexpr (TP) {
+    __shared__ int bnd_s[128];
+    bnd_lds = bnd_s;
+    tp_stage_bounds(cu_seqlens, row0, len, kb, bnd_lds);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
+
+  // TP: the bounds of the four OWNED key rows; a query row is live for a
+  // key when it lies inside the key's sequence, [klo, khi) relative to row0
+  int klo[4] = {}, khi[4] = {};
+  if constexpr (TP) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      klo[r] = bnd_lds[2 * (kr + (lane >> 4) * 4 + r)];
+      khi[r] = bnd_lds[2 * (kr + (lane >> 4) * 4 + r) + 1];
+    }
+  }
 
   float mv[4];
 #pragma unroll
@@ -639,14 +753,19 @@ void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
         pt[j][r] = exp2f(acc_st[j][r] * scale2 + mv[r] - lse_j);
         // tail query rows have no lse/dvec (lse_lds holds nothing there):
         // their P^T is 0 by index, never by arithmetic on that slot
-        if (VARLEN && qrow >= len) pt[j][r] = 0.f;
+        // TP: query rows of another sequence too (their lse is not this
+        // key's: the exp2 above may have overflowed)
+        if (TP ? (qrow < klo[r] || qrow >= khi[r]) : (VARLEN && qrow >= len))
+          pt[j][r] = 0.f;
         live[j][r] = true;
         if (DROP) {
           const unsigned int grow =
               VARLEN ? (unsigned int)(stat0 + qrow)
                      : (unsigned int)bh * S + (unsigned int)qrow;
           const unsigned int rr = hash_rng32(
-              seed32, drop_idx<VARLEN>(grow, (unsigned int)gkey, S));
+              seed32,
+              drop_idx<VARLEN>(
+                  grow, (unsigned int)(gkey - (TP ? klo[r] : 0)), S));
           live[j][r] = (rr * 2.3283064365386963e-10f) >= p;
         }
       }
@@ -688,7 +807,9 @@ void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
         const float dvec_j = dvec_lds[qrow];
         const float dpt = live[j][r] ? acc_dpt[j][r] * inv_keep : 0.f;
         float dsv = pt[j][r] * (dpt - dvec_j) * scale;
-        if (VARLEN && qrow >= len) dsv = 0.f;  // dvec_j is not data there
+        // dvec_j is not data there (TP: not this key's sequence)
+        if (TP ? (qrow < klo[r] || qrow >= khi[r]) : (VARLEN && qrow >= len))
+          dsv = 0.f;
         const int qcol = j * 16 + (lane & 15);
         *reinterpret_cast<unsigned short*>(
             pds_lds + tr_addr(prow, qcol)) =
@@ -725,6 +846,80 @@ void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
       dkbase[gkey * ld + jd * 16 + ccol] = from_f32<T>(acc_dk[jd][r]);
       dvbase[gkey * ld + jd * 16 + ccol] = from_f32<T>(acc_dv[jd][r]);
     }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// tile plan of the TP instantiations: one workgroup, once per model forward
+// ---------------------------------------------------------------------------
+
+constexpr int TP_MAX_SEQS = 4096;  // cu_seqlens is staged in LDS
+
+// Walks the sequences in order. A sequence of more than 64 rows gives one
+// item per 64-row tile of itself (the live blocks of the VARLEN grid);
+// consecutive sequences of at most 64 rows are collected greedily into a
+// group, which closes when the next one would take it past 64 rows or is
+// long, and is one item of contiguous rows [g0, g0 + n). Empty sequences
+// give nothing. Lengths are clamped as varlen_len clamps them. Thread 0
+// does the greedy pass over LDS; the per-row bounds are filled in parallel
+// by a binary search (cu_seqlens ascending is the callers' precondition).
+__global__ __launch_bounds__(NTHREADS)
+void fa_tile_plan_kernel(const int* __restrict__ cu_seqlens, int B, int T,
+                         int max_items, int* __restrict__ plan) {
+  __shared__ int cu[TP_MAX_SEQS + 1];
+  int* items = plan + TP_ITEMS;
+  int* bnd = items + 4 * (long)max_items;
+  for (int i = threadIdx.x; i <= B; i += NTHREADS) {
+    const int c = cu_seqlens[i];
+    cu[i] = c < 0 ? 0 : c > T ? T : c;
+  }
+  for (int i = threadIdx.x; i < 4 * max_items; i += NTHREADS) items[i] = 0;
+  if (threadIdx.x < TP_ITEMS) plan[threadIdx.x] = 0;
+  __syncthreads();
+
+  for (int r = threadIdx.x; r < T; r += NTHREADS) {
+    int lo = 0, hi = B + 1;  // first index whose cu is past row r
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (cu[mid] > r) hi = mid; else lo = mid + 1;
+    }
+    int s = 0, e = 0;  // rows outside every sequence: start == end
+    if (lo >= 1 && lo <= B) {
+      s = cu[lo - 1];
+      e = cu[lo] - s > 1024 ? s + 1024 : cu[lo];
+      if (r >= e) s = e = 0;
+    }
+    *reinterpret_cast<int2*>(bnd + 2 * (long)r) = make_int2(s, e);
+  }
+
+  if (threadIdx.x == 0) {
+    int n_items = 0, g0 = 0, gn = 0;
+    auto emit = [&](int r0, int n, int tile) {
+      if (n_items < max_items)  // holds by the host bound; guards bad input
+        *reinterpret_cast<int4*>(items + 4 * n_items) =
+            make_int4(r0, n, tile, 0);
+      ++n_items;
+    };
+    for (int b = 0; b < B; ++b) {
+      const int s0 = cu[b];
+      int n = cu[b + 1] - s0;
+      n = n > 1024 ? 1024 : n;
+      if (n <= 0) continue;
+      if (n > 64) {
+        if (gn) emit(g0, gn, 0);
+        gn = 0;
+        for (int t = 0; t * 64 < n; ++t) emit(s0, n, t);
+      } else {
+        if (gn && (g0 + gn != s0 || gn + n > 64)) {
+          emit(g0, gn, 0);
+          gn = 0;
+        }
+        if (!gn) g0 = s0;
+        gn += n;
+      }
+    }
+    if (gn) emit(g0, gn, 0);
+    plan[TP_COUNT] = n_items < max_items ? n_items : max_items;
   }
 }
 
@@ -798,16 +993,20 @@ static FaLaunch fa_launch_setup(const torch::Tensor& mask, long seq_max,
     }                                                                          \
   })
 
-template <bool VARLEN>
+// TP (tile-packed): cu_seqlens carries the tile plan and the grid is
+// (tp_items, nh), one block per plan slot and head
+template <bool VARLEN, bool TP = false>
 static void fa_fwd_launch(const torch::Tensor& qkv, const torch::Tensor& mask,
                           torch::Tensor& o, torch::Tensor& lse,
                           const int* cu_seqlens, long seq_max, long batch,
                           long S, long nh, double scale, double p,
-                          const torch::Tensor& seed_buf, long salt) {
-  const FaLaunch L = fa_launch_setup(mask, seq_max, batch * nh, p, seed_buf);
+                          const torch::Tensor& seed_buf, long salt,
+                          long tp_items = 0) {
+  FaLaunch L = fa_launch_setup(mask, seq_max, batch * nh, p, seed_buf);
+  if (TP) L.grid = dim3(tp_items, nh);
   FA_DISPATCH(qkv.scalar_type(), L, VARLEN, [&] {
     hipLaunchKernelGGL(
-        (fa_fwd_kernel<scalar_t, V8, HAS_MASK, DROP, PRELOAD, VARLEN>), L.grid,
+        (fa_fwd_kernel<scalar_t, V8, HAS_MASK, DROP, PRELOAD, VARLEN, TP>), L.grid,
         dim3(NTHREADS), 0, L.stream, (const scalar_t*)qkv.data_ptr(),
         HAS_MASK ? (const scalar_t*)mask.data_ptr() : nullptr,
         (scalar_t*)o.data_ptr(), (float*)lse.data_ptr(), L.seed,
@@ -818,15 +1017,17 @@ static void fa_fwd_launch(const torch::Tensor& qkv, const torch::Tensor& mask,
 
 // Dvec = rowsum(dO*O) is computed inside the dQ pass (it already stages dO;
 // O goes through the dS buffer) and consumed by dK/dV
-template <bool VARLEN>
+template <bool VARLEN, bool TP = false>
 static void fa_bwd_launch(const torch::Tensor& dout, const torch::Tensor& qkv,
                           const torch::Tensor& o, const torch::Tensor& lse,
                           const torch::Tensor& mask, torch::Tensor& dvec,
                           torch::Tensor& dqkv, const int* cu_seqlens,
                           long seq_max, long batch, long S, long nh,
                           double scale, double p,
-                          const torch::Tensor& seed_buf, long salt) {
-  const FaLaunch L = fa_launch_setup(mask, seq_max, batch * nh, p, seed_buf);
+                          const torch::Tensor& seed_buf, long salt,
+                          long tp_items = 0) {
+  FaLaunch L = fa_launch_setup(mask, seq_max, batch * nh, p, seed_buf);
+  if (TP) L.grid = dim3(tp_items, nh);
   FA_DISPATCH(qkv.scalar_type(), L, VARLEN, [&] {
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(
@@ -838,8 +1039,8 @@ static void fa_bwd_launch(const torch::Tensor& dout, const torch::Tensor& qkv,
           (scalar_t*)dqkv.data_ptr(), L.seed, (unsigned long long)salt,
           (float)scale, (float)p, (int)nh, (int)S, cu_seqlens);
     };
-    launch(fa_bwd_dq_kernel<scalar_t, V8, HAS_MASK, DROP, PRELOAD, VARLEN>);
-    launch(fa_bwd_dkv_kernel<scalar_t, V8, HAS_MASK, DROP, PRELOAD, VARLEN>);
+    launch(fa_bwd_dq_kernel<scalar_t, V8, HAS_MASK, DROP, PRELOAD, VARLEN, TP>);
+    launch(fa_bwd_dkv_kernel<scalar_t, V8, HAS_MASK, DROP, PRELOAD, VARLEN, TP>);
   });
 }
 
@@ -942,5 +1143,104 @@ torch::Tensor flash_attn_varlen_bwd(torch::Tensor dout, torch::Tensor qkv,
   fa_bwd_launch<true>(dout, qkv, o, lse, torch::Tensor(), dvec, dqkv,
                       (const int*)cu_seqlens.data_ptr(), max_seqlen, B, S, nh,
                       scale, p, seed_buf, salt);
+  return dqkv;
+}
+
+// ---------------------------------------------------------------------------
+// tile-packed entry points: the VARLEN kernels over a tile plan, in which a
+// 64-row tile holds several whole consecutive short sequences
+// ---------------------------------------------------------------------------
+
+// Upper bound on the plan's item count from (T, B) alone; it sizes the item
+// list and the attention grid, so no launch depends on the boundaries.
+// Let R <= T be the rows inside sequences.
+//  (a) A long sequence of L > 64 rows gives ceil(L/64) <= floor(L/64) + 1
+//      items, a group is one item and holds at least one sequence, so
+//      items <= floor(R/64) + (long sequences + groups) <= T/64 + B.
+//  (b) A group closes only when the next short sequence would take it past
+//      64 rows, so two groups in a row hold at least 65 rows together and a
+//      run of k groups between long sequences holds >= 65*floor(k/2) rows:
+//      k <= 2*rows/65 + 1. A long sequence has L >= 65, so its ceil(L/64)
+//      <= (L + 63)/64 <= (L + 63*L/65)/64 = 2*L/65 items. With n long
+//      sequences of R_l rows in all there are at most n + 1 runs and
+//      n <= R_l/65, so items <= 2*R/65 + n + 1 <= 3*R/65 + 1 <= 3*T/65 + 1.
+long flash_attn_tilepack_max_items(long T, long B) {
+  const long a = T / 64 + B, b = 3 * T / 65 + 1;
+  return std::max(1L, std::min(a, b));
+}
+
+torch::Tensor flash_attn_tilepack_plan(torch::Tensor cu_seqlens, long T) {
+  TORCH_CHECK(cu_seqlens.is_cuda() && cu_seqlens.is_contiguous() &&
+                  cu_seqlens.dim() == 1 && cu_seqlens.numel() >= 2 &&
+                  cu_seqlens.scalar_type() == torch::kInt,
+              "flash_attn_tilepack: cu_seqlens must be a contiguous cuda "
+              "int32 [B+1]");
+  TORCH_CHECK(T > 0 && T % 64 == 0 && T <= (1L << 22),
+              "flash_attn_tilepack: total_rows must be a positive multiple "
+              "of 64, at most 2^22");
+  const long B = cu_seqlens.numel() - 1;
+  TORCH_CHECK(B <= TP_MAX_SEQS, "flash_attn_tilepack: more than ",
+              TP_MAX_SEQS, " sequences unsupported (cu_seqlens is staged in "
+              "LDS)");
+  const long M = flash_attn_tilepack_max_items(T, B);
+  auto plan = torch::empty({TP_ITEMS + 4 * M + 2 * T}, cu_seqlens.options());
+  hipLaunchKernelGGL(fa_tile_plan_kernel, dim3(1), dim3(NTHREADS), 0,
+                     at::hip::getCurrentHIPStream(),
+                     (const int*)cu_seqlens.data_ptr(), (int)B, (int)T, (int)M,
+                     (int*)plan.data_ptr());
+  return plan;
+}
+
+// item slots of a plan buffer made for T rows; rejects any other buffer
+static long check_fa_tilepack_plan(const torch::Tensor& plan, long T) {
+  TORCH_CHECK(plan.is_cuda() && plan.is_contiguous() && plan.dim() == 1 &&
+                  plan.scalar_type() == torch::kInt,
+              "flash_attn_tilepack: plan must be the contiguous cuda int32 "
+              "buffer of flash_attn_tilepack_plan");
+  const long rest = plan.numel() - TP_ITEMS - 2 * T;
+  TORCH_CHECK(rest >= 4 && rest % 4 == 0 &&
+                  rest / 4 <= flash_attn_tilepack_max_items(T, TP_MAX_SEQS),
+              "flash_attn_tilepack: plan was not built for total_rows = ", T);
+  return rest / 4;
+}
+
+std::vector<torch::Tensor> flash_attn_tilepack_fwd(torch::Tensor qkv,
+                                                   torch::Tensor plan,
+                                                   long max_seqlen, long nh,
+                                                   double scale, double p,
+                                                   torch::Tensor seed_buf,
+                                                   long salt) {
+  check_fa_varlen_args(qkv, plan, max_seqlen, nh);
+  const long S = qkv.size(0), H = (long)nh * 64;
+  const long M = check_fa_tilepack_plan(plan, S);
+  auto o = torch::zeros({S, H}, qkv.options());  // see flash_attn_varlen_fwd
+  auto lse = torch::empty({nh, S}, qkv.options().dtype(torch::kFloat));
+  fa_fwd_launch<true, true>(qkv, torch::Tensor(), o, lse,
+                            (const int*)plan.data_ptr(), max_seqlen, 1, S, nh,
+                            scale, p, seed_buf, salt, M);
+  return {o, lse};
+}
+
+torch::Tensor flash_attn_tilepack_bwd(torch::Tensor dout, torch::Tensor qkv,
+                                      torch::Tensor o, torch::Tensor lse,
+                                      torch::Tensor plan, long max_seqlen,
+                                      long nh, double scale, double p,
+                                      torch::Tensor seed_buf, long salt) {
+  check_fa_varlen_args(qkv, plan, max_seqlen, nh);
+  const long S = qkv.size(0), H = (long)nh * 64;
+  const long M = check_fa_tilepack_plan(plan, S);
+  TORCH_CHECK(dout.is_cuda() && dout.is_contiguous() &&
+                  dout.scalar_type() == qkv.scalar_type() &&
+                  dout.dim() == 2 && dout.size(0) == S && dout.size(1) == H,
+              "flash_attn_tilepack: dout must be contiguous [T, H] of qkv "
+              "dtype");
+  TORCH_CHECK(o.is_contiguous() && o.sizes() == dout.sizes() &&
+                  lse.is_contiguous() && lse.numel() == nh * S,
+              "flash_attn_tilepack: o [T, H] / lse [nh, T] from the forward");
+  auto dqkv = torch::zeros_like(qkv);  // see flash_attn_varlen_fwd
+  auto dvec = torch::empty({nh, S}, qkv.options().dtype(torch::kFloat));
+  fa_bwd_launch<true, true>(dout, qkv, o, lse, torch::Tensor(), dvec, dqkv,
+                            (const int*)plan.data_ptr(), max_seqlen, 1, S, nh,
+                            scale, p, seed_buf, salt, M);
   return dqkv;
 }

@@ -110,6 +110,19 @@ torch::Tensor flash_attn_varlen_bwd(torch::Tensor dout, torch::Tensor qkv,
                                     torch::Tensor cu_seqlens, long max_seqlen,
                                     long nh, double scale, double p,
                                     torch::Tensor seed_buf, long salt);
+long flash_attn_tilepack_max_items(long T, long B);
+torch::Tensor flash_attn_tilepack_plan(torch::Tensor cu_seqlens, long T);
+std::vector<torch::Tensor> flash_attn_tilepack_fwd(torch::Tensor qkv,
+                                                   torch::Tensor plan,
+                                                   long max_seqlen, long nh,
+                                                   double scale, double p,
+                                                   torch::Tensor seed_buf,
+                                                   long salt);
+torch::Tensor flash_attn_tilepack_bwd(torch::Tensor dout, torch::Tensor qkv,
+                                      torch::Tensor o, torch::Tensor lse,
+                                      torch::Tensor plan, long max_seqlen,
+                                      long nh, double scale, double p,
+                                      torch::Tensor seed_buf, long salt);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_fwd", &layernorm_fwd);
@@ -163,4 +176,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn_qkv_bwd", &flash_attn_qkv_bwd);
   m.def("flash_attn_varlen_fwd", &flash_attn_varlen_fwd);
   m.def("flash_attn_varlen_bwd", &flash_attn_varlen_bwd);
+  m.def("flash_attn_tilepack_max_items", &flash_attn_tilepack_max_items);
+  m.def("flash_attn_tilepack_plan", &flash_attn_tilepack_plan);
+  m.def("flash_attn_tilepack_fwd", &flash_attn_tilepack_fwd);
+  m.def("flash_attn_tilepack_bwd", &flash_attn_tilepack_bwd);
 }

@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip_enabled, ext
+from .tile_plan import AttnTilePlan, plan_from_reference, plan_views
 
 
 # --------------------------------------------------------------------------
@@ -522,9 +523,54 @@ class _FlashAttnVarlenFn(torch.autograd.Function):
         return dqkv, None, None, None, None, None
 
 
+class _FlashAttnTilePackFn(torch.autograd.Function):
+    """_FlashAttnVarlenFn over a tile plan (``varlen_attention_plan``): the
+    tile-packed kernel instantiations, in which one 64-row tile holds
+    several whole consecutive short sequences. Same layouts, same dropout
+    masks and the same zero rows as the per-sequence kernels."""
+
+    @staticmethod
+    def forward(ctx, qkv, plan_buf, max_seqlen, nh, scale, p_drop):
+        if p_drop > 0.0:
+            seed_buf, salt = _dropout_seed.get(qkv.device)
+        else:
+            seed_buf, salt = torch.Tensor(), 0
+        o, lse = ext().flash_attn_tilepack_fwd(qkv, plan_buf, max_seqlen, nh,
+                                               scale, p_drop, seed_buf, salt)
+        ctx.save_for_backward(qkv, o, lse, plan_buf,
+                              seed_buf if p_drop > 0.0 else torch.Tensor())
+        ctx.max_seqlen = max_seqlen
+        ctx.nh, ctx.scale, ctx.p, ctx.salt = nh, scale, p_drop, salt
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, lse, plan_buf, seed_buf = ctx.saved_tensors
+        dqkv = ext().flash_attn_tilepack_bwd(
+            do.contiguous(), qkv, o, lse, plan_buf, ctx.max_seqlen, ctx.nh,
+            ctx.scale, ctx.p, seed_buf, ctx.salt)
+        return dqkv, None, None, None, None, None
+
+
+def varlen_attention_plan(cu_seqlens: torch.Tensor,
+                          total_rows: int) -> AttnTilePlan:
+    """Tile plan of tile-packed attention for a packed batch of
+    ``total_rows`` rows (see ops/tile_plan.py). A pure function of the
+    contents of ``cu_seqlens``; on the HIP path one small launch with no
+    host sync, so a captured graph stays valid for any boundaries. Build it
+    once per model forward and hand it to every ``attention_varlen``."""
+    total_rows = int(total_rows)
+    if hip_enabled(cu_seqlens) and total_rows % 64 == 0:
+        return plan_views(
+            ext().flash_attn_tilepack_plan(cu_seqlens.contiguous(),
+                                           total_rows), total_rows)
+    return plan_from_reference(cu_seqlens, total_rows)
+
+
 def attention_varlen(qkv: torch.Tensor, cu_seqlens: torch.Tensor,
                      max_seqlen: int, num_heads: int, dropout_p: float = 0.0,
-                     training: bool = False) -> torch.Tensor:
+                     training: bool = False,
+                     plan: Optional[AttnTilePlan] = None) -> torch.Tensor:
     """Attention on a packed (padding-free) QKV projection output.
 
     qkv: [T, 3H]; sequence b occupies rows cu_seqlens[b]..cu_seqlens[b+1]
@@ -533,13 +579,19 @@ def attention_varlen(qkv: torch.Tensor, cu_seqlens: torch.Tensor,
     sequence are exactly zero, forward and backward. On a ROCm GPU with
     head_dim 64, T%64==0 and bf16/fp16 this runs the fused MFMA flash
     kernel; otherwise a per-sequence loop over :func:`attention` (which
-    reads cu_seqlens on the host)."""
+    reads cu_seqlens on the host). With a ``plan`` of
+    :func:`varlen_attention_plan` the fused path runs the tile-packed
+    kernels; the per-sequence loop ignores it."""
     T, H3 = qkv.shape
     H = H3 // 3
     hd = H // num_heads
     p_eff = float(dropout_p if training else 0.0)
     if hip_enabled(qkv) and hd == 64 and T % 64 == 0 \
             and qkv.dtype in (torch.bfloat16, torch.float16):
+        if plan is not None:
+            return _FlashAttnTilePackFn.apply(
+                qkv.contiguous(), plan.buf, int(max_seqlen), num_heads,
+                1.0 / math.sqrt(hd), p_eff)
         return _FlashAttnVarlenFn.apply(
             qkv.contiguous(), cu_seqlens.contiguous(), int(max_seqlen),
             num_heads, 1.0 / math.sqrt(hd), p_eff)

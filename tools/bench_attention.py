@@ -1,24 +1,139 @@
-import sys, time, torch
-sys.path.insert(0, ".")
-from pdnlp_amd.ops import ext
-e = ext()
+"""Attention kernel timings.
+
+    python tools/bench_attention.py            # padded kernels, wall clock
+    python tools/bench_attention.py --packed   # per-sequence vs tile-packed
+
+``--packed`` times the per-sequence (VARLEN) and the tile-packed kernels,
+forward and backward, on one stand-in token-budget batch of ``--rows``
+packed rows (tools/bench_unpad.py's seeded lognormal lengths, batched by
+TokenBudgetBatchSampler), BERT-base heads, bf16, random data. Device events
+around ``--iters`` launches; the modes alternate for ``--rounds`` rounds in
+one process and the per-round means are reported with their range. The plan
+kernel (once per model forward, not per layer) is timed on its own.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from pdnlp_amd.ops import ext  # noqa: E402
+
 dev = "cuda:0"
-torch.manual_seed(0)
-for (B, nh, S) in [(16, 16, 512), (32, 12, 128)]:
+
+
+def padded():
+    e = ext()
+    torch.manual_seed(0)
+    for (B, nh, S) in [(16, 16, 512), (32, 12, 128)]:
+        H = nh * 64
+        qkv = (torch.randn(B, S, 3*H, device=dev) / 28).bfloat16()
+        mask = torch.zeros(B, 1, 1, S, device=dev, dtype=torch.bfloat16).reshape(B, S).contiguous()
+        o, lse = e.flash_attn_qkv_fwd(qkv, mask, nh, 0.125, 0.0, torch.Tensor(), 0)
+        do = torch.randn_like(o)
+        def t_fwd():
+            return e.flash_attn_qkv_fwd(qkv, mask, nh, 0.125, 0.0, torch.Tensor(), 0)
+        def t_bwd():
+            return e.flash_attn_qkv_bwd(do, qkv, o, lse, mask, nh, 0.125, 0.0, torch.Tensor(), 0)
+        for name, fn in (("fwd", t_fwd), ("bwd", t_bwd)):
+            for _ in range(5): fn()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(30): fn()
+            torch.cuda.synchronize()
+            us = (time.perf_counter()-t0)/30*1e6
+            print(f"B{B} nh{nh} S{S} {name}: {us:.0f} us")
+
+
+def event_us(fn, iters):
+    t0, t1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+    t0.record()
+    for _ in range(iters):
+        fn()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) * 1e3 / iters
+
+
+def packed(a):
+    from bench_unpad import lengths
+    from pdnlp_amd.data import SEQ_MULTIPLE, TokenBudgetBatchSampler
+    from pdnlp_amd.ops import tile_plan_max_items, tile_plan_reference
+    e = ext()
+    nh, T, p = 12, a.rows, a.dropout
     H = nh * 64
-    qkv = (torch.randn(B, S, 3*H, device=dev) / 28).bfloat16()
-    mask = torch.zeros(B, 1, 1, S, device=dev, dtype=torch.bfloat16).reshape(B, S).contiguous()
-    o, lse = e.flash_attn_qkv_fwd(qkv, mask, nh, 0.125, 0.0, torch.Tensor(), 0)
-    do = torch.randn_like(o)
-    def t_fwd():
-        return e.flash_attn_qkv_fwd(qkv, mask, nh, 0.125, 0.0, torch.Tensor(), 0)
-    def t_bwd():
-        return e.flash_attn_qkv_bwd(do, qkv, o, lse, mask, nh, 0.125, 0.0, torch.Tensor(), 0)
-    for name, fn in (("fwd", t_fwd), ("bwd", t_bwd)):
-        for _ in range(5): fn()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(30): fn()
-        torch.cuda.synchronize()
-        us = (time.perf_counter()-t0)/30*1e6
-        print(f"B{B} nh{nh} S{S} {name}: {us:.0f} us")
+    source, lens = lengths(9200, 123, "./data/train.json")
+    batch = TokenBudgetBatchSampler(lens, T, seed=7).batches[a.batch_index]
+    bl = [lens[i] for i in batch]
+    nseq = (len(bl) + SEQ_MULTIPLE - 1) // SEQ_MULTIPLE * SEQ_MULTIPLE
+    cu = [0]
+    for n in bl + [0] * (nseq - len(bl)):   # empty sequences, as the collate
+        cu.append(cu[-1] + n)
+    items, _ = tile_plan_reference(cu, T)
+    live = sum((n + 63) // 64 for n in bl)
+    grid_ps = (max(bl) + 63) // 64 * nseq
+    print(f"{source}: {len(bl)} sentences ({nseq} slots), {cu[-1]} of {T} "
+          f"rows real, longest {max(bl)}")
+    print(f"per head: per-sequence grid {grid_ps} blocks, {live} live; "
+          f"tile-packed grid {tile_plan_max_items(T, nseq)} blocks, "
+          f"{len(items)} live")
+    torch.manual_seed(0)
+    qkv = torch.randn(T, 3 * H, device=dev).bfloat16()
+    do = torch.randn(T, H, device=dev).bfloat16()
+    cu_t = torch.tensor(cu, dtype=torch.int32, device=dev)
+    seed = torch.tensor([1234], dtype=torch.int64, device=dev) if p \
+        else torch.Tensor()
+    mx, sc = 128, 0.125
+    plan = e.flash_attn_tilepack_plan(cu_t, T)
+    assert plan[0].item() == len(items)
+    o_ps, lse_ps = e.flash_attn_varlen_fwd(qkv, cu_t, mx, nh, sc, p, seed, 1)
+    o_tp, lse_tp = e.flash_attn_tilepack_fwd(qkv, plan, mx, nh, sc, p, seed, 1)
+    fns = {
+        "per_sequence_fwd": lambda: e.flash_attn_varlen_fwd(
+            qkv, cu_t, mx, nh, sc, p, seed, 1),
+        "tile_packed_fwd": lambda: e.flash_attn_tilepack_fwd(
+            qkv, plan, mx, nh, sc, p, seed, 1),
+        "per_sequence_bwd": lambda: e.flash_attn_varlen_bwd(
+            do, qkv, o_ps, lse_ps, cu_t, mx, nh, sc, p, seed, 1),
+        "tile_packed_bwd": lambda: e.flash_attn_tilepack_bwd(
+            do, qkv, o_tp, lse_tp, plan, mx, nh, sc, p, seed, 1),
+        "plan": lambda: e.flash_attn_tilepack_plan(cu_t, T),
+    }
+    for fn in fns.values():
+        for _ in range(10):
+            fn()
+    torch.cuda.synchronize()
+    us = {k: [] for k in fns}
+    for _ in range(a.rounds):
+        for k, fn in fns.items():
+            us[k].append(event_us(fn, a.iters))
+    for k, v in us.items():
+        print(f"{k}: {min(v):.1f} .. {max(v):.1f} us over {a.rounds} rounds "
+              f"of {a.iters} launches (each with its output allocation)")
+    for d in ("fwd", "bwd"):
+        ps, tp = us[f"per_sequence_{d}"], us[f"tile_packed_{d}"]
+        print(f"{d}: ranges disjoint in favour of tile-packed: "
+              f"{max(tp) < min(ps)}; of per-sequence: {max(ps) < min(tp)}")
+    print(json.dumps({"metric": "bench_attention_packed", "rows": T,
+                      "dropout": p, "sentences": len(bl),
+                      "live_blocks_per_head": {"per_sequence": live,
+                                               "tile_packed": len(items)},
+                      "us": us}))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--packed", action="store_true")
+    ap.add_argument("--rows", type=int, default=4096)
+    ap.add_argument("--batch-index", type=int, default=0)
+    ap.add_argument("--dropout", type=float, default=0.1)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=50)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_attention.py measures GPU kernels: no GPU visible")
+    packed(args) if args.packed else padded()

@@ -20,6 +20,10 @@ per mode: every window, the ms/step range, real sentences per step,
 samples/s (range), and ``memory_reserved`` after ``--mem-steps`` steps from
 an emptied allocator cache. Ranges that overlap are reported as such.
 
+With ``--attn-tile-pack true`` every budget also runs with tile-packed
+attention (``tokensN_tp``, same batches, same windows), next to the same
+build with the option off.
+
 With ``--hip-graph true`` every mode also runs through the Trainer's
 hipGraph cache: graphs captured, the share of an epoch's steps that
 GraphPolicy replays from a cold start, and replay windows interleaved in
@@ -120,6 +124,7 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--mem-steps", type=int, default=200)
     ap.add_argument("--hip-graph", default="false")
+    ap.add_argument("--attn-tile-pack", default="false")
     ap.add_argument("--seed", type=int, default=123)
     ap.add_argument("--data-path", default="./data/train.json")
     a = ap.parse_args()
@@ -127,6 +132,7 @@ def main():
         sys.exit("bench_tokens.py measures GPU step time: no GPU visible")
     dev = torch.device("cuda:0")
     use_graph = a.hip_graph.lower() in ("1", "true", "yes")
+    tile_pack = a.attn_tile_pack.lower() in ("1", "true", "yes")
     budgets = [int(x) for x in a.budgets.split(",")]
     print(f"device: {torch.cuda.get_device_name(0)}")
 
@@ -166,11 +172,16 @@ def main():
               f"{share * 100:.1f} % of the first epoch's steps replayed")
         epochs[name] = [to_device(b, dev) for b in timed]
 
-    modes = [Mode(name, ep, dev) for name, ep in epochs.items()]
+    # (mode name, pool name, tile-packed attention)
+    runs = [(name, name, False) for name in epochs]
+    if tile_pack:
+        runs += [(name + "_tp", name, True) for name in epochs
+                 if name.startswith("tokens")]
+    modes = [Mode(name, epochs[ep], dev, tp) for name, ep, tp in runs]
     graph_modes = []
     if use_graph:
-        graph_modes = [GraphMode(name + "_graph", ep, dev)
-                       for name, ep in epochs.items()]
+        graph_modes = [GraphMode(name + "_graph", epochs[ep], dev, tp)
+                       for name, ep, tp in runs]
     for m in modes + graph_modes:            # every batch of the pool, once
         m.window(len(m.batches))
     for m in graph_modes:
@@ -196,7 +207,7 @@ def main():
 
     result = {}
     for name, v in times.items():
-        base = name.replace("_graph", "")
+        base = name.replace("_graph", "").replace("_tp", "")
         sps = info[base]["sentences_per_step"]
         result[name] = {
             "ms_per_step": v, "range_ms": [min(v), max(v)],
@@ -210,6 +221,14 @@ def main():
         r["vs_baseline"] = ("above" if lo > base[1] else
                             "below" if hi < base[0] else "overlapping")
         print(f"{name} samples/s against unpad{a.batch}: {r['vs_baseline']}")
+    for name, r in result.items():   # option on against off, same batches
+        if "_tp" in name:
+            lo, hi = r["range_ms"]
+            off = result[name.replace("_tp", "")]["range_ms"]
+            r["vs_option_off"] = ("faster" if hi < off[0] else
+                                  "slower" if lo > off[1] else "overlapping")
+            print(f"{name} ms/step {lo:.3f} .. {hi:.3f} against option off "
+                  f"{off[0]:.3f} .. {off[1]:.3f}: {r['vs_option_off']}")
 
     # memory: one mode resident at a time would need a rebuild; report the
     # growth of memory_reserved over mem-steps from an emptied cache instead
