@@ -88,6 +88,7 @@ from .functional import (  # noqa: F401,E402
     dropout,
     reseed_dropout,
     dw_stream_join,
+    inference_kernels,
 )
 from .tile_plan import (  # noqa: F401,E402
     AttnTilePlan,

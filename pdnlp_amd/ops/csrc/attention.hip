@@ -43,6 +43,8 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include <optional>
+
 #include "gemm_common.h"  // vector typedefs, mfma16
 
 namespace {
@@ -214,12 +216,38 @@ __device__ __forceinline__ void tp_stage_bounds(const int* plan, long row0,
   }
 }
 
+// INFER forward: the output is not zero-filled by the host, so the rows
+// outside every sequence (plan bounds start == end) are zeroed here, with no
+// launch of their own. The grid is (M, nh) with M >= T/64 (both arms of
+// flash_attn_tilepack_max_items are; host-checked): block (x, h) with
+// x < T/64 zeroes head h's 64 columns of the free rows of stripe x, four
+// lanes of 16 columns per row. No item stores a free row (items cover
+// sequence rows only, clamped as the bounds are), so nothing races, and all
+// of it is ordinary loads and stores before any barrier or LDS load.
+template <typename T>
+__device__ __forceinline__ void tp_zero_free_rows(const int* plan,
+                                                  T* __restrict__ o, int T_rows,
+                                                  int nh, long h) {
+  const long g = (long)blockIdx.x * 64 + (threadIdx.x >> 2);
+  if (g >= T_rows) return;
+  const int2 be = *reinterpret_cast<const int2*>(
+      plan + TP_ITEMS + 4 * (long)gridDim.x + 2 * g);
+  if (be.x != be.y) return;
+  uint4* dst = reinterpret_cast<uint4*>(o + g * ((long)nh * 64) + h * 64 +
+                                        (threadIdx.x & 3) * 16);
+  dst[0] = make_uint4(0u, 0u, 0u, 0u);
+  dst[1] = make_uint4(0u, 0u, 0u, 0u);
+}
+
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
 
+// INFER (serving; TP without dropout or mask only): no lse store, and the
+// output arrives uninitialised instead of zero-filled, so the kernel writes
+// the zero rows itself (see tp_zero_free_rows).
 template <typename T, typename V8, bool HAS_MASK, bool DROP, bool PRELOAD,
-          bool VARLEN, bool TP>
+          bool VARLEN, bool TP, bool INFER = false>
 __global__ __launch_bounds__(NTHREADS)
 void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
                    T* __restrict__ o, float* __restrict__ lse,
@@ -227,8 +255,12 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
                    unsigned long long salt, float scale, float p,
                    int nh, int S, const int* __restrict__ cu_seqlens) {
   scale *= 1.4426950408889634f;  // exp2 domain (log2 e)
+  static_assert(!INFER || (TP && VARLEN && !DROP && !HAS_MASK),
+                "INFER is a tile-packed, dropout-free, mask-free form");
   const int bh = blockIdx.y;
   const long b = TP ? 0 : bh / nh, h = TP ? bh : bh % nh;
+  // before the item count is looked at: a block past it still owns a stripe
+  if constexpr (INFER) tp_zero_free_rows<T>(cu_seqlens, o, S, nh, h);
   // TP: cu_seqlens carries the tile plan, blockIdx.x an item of it
   if (TP && (int)blockIdx.x >= cu_seqlens[TP_COUNT]) return;  // block-uniform
   const int* item =
@@ -407,7 +439,7 @@ void fa_fwd_kernel(const T* __restrict__ qkv, const T* __restrict__ mask,
 #pragma unroll
     for (int jd = 0; jd < 4; ++jd)
       obase[grow * H + jd * 16 + ccol] = from_f32<T>(acc_o[jd][r] * invl);
-    if (ccol == 0)
+    if (!INFER && ccol == 0)
       lse[stat0 + grow] = m[r] + log2f(fmaxf(l[r], 1e-30f));
   }
 }
@@ -1243,4 +1275,54 @@ torch::Tensor flash_attn_tilepack_bwd(torch::Tensor dout, torch::Tensor qkv,
                             (const int*)plan.data_ptr(), max_seqlen, 1, S, nh,
                             scale, p, seed_buf, salt, M);
   return dqkv;
+}
+
+// the four INFER instantiations: PRELOAD x {bf16, fp16}
+template <typename T, typename V8>
+static void fa_infer_launch(const torch::Tensor& qkv, const torch::Tensor& plan,
+                            torch::Tensor& o, dim3 grid, long max_seqlen,
+                            long nh, double scale) {
+  DISPATCH_BOOL(max_seqlen <= 128, PRELOAD, [&] {
+    hipLaunchKernelGGL(
+        (fa_fwd_kernel<T, V8, false, false, PRELOAD, true, true, true>), grid,
+        dim3(NTHREADS), 0, at::hip::getCurrentHIPStream(),
+        (const T*)qkv.data_ptr(), (const T*)nullptr, (T*)o.data_ptr(),
+        (float*)nullptr, (const unsigned long long*)nullptr, 0ull,
+        (float)scale, 0.f, (int)nh, (int)qkv.size(0),
+        (const int*)plan.data_ptr());
+  });
+}
+
+// Serving form of flash_attn_tilepack_fwd at p = 0: the INFER instantiations.
+// No lse, no fill launch: o is torch::empty (or the caller's out) and comes
+// back with the bits of flash_attn_tilepack_fwd's o, zero rows included.
+torch::Tensor flash_attn_tilepack_infer(torch::Tensor qkv, torch::Tensor plan,
+                                        long max_seqlen, long nh, double scale,
+                                        std::optional<torch::Tensor> out) {
+  check_fa_varlen_args(qkv, plan, max_seqlen, nh);
+  const long S = qkv.size(0), H = (long)nh * 64;
+  const long M = check_fa_tilepack_plan(plan, S);
+  // the zero rows of stripe x are written by blocks (x, *)
+  TORCH_CHECK(M >= S / 64, "flash_attn_tilepack_infer: the plan has fewer "
+              "item slots than total_rows / 64");
+  torch::Tensor o;
+  if (out.has_value() && out->defined()) {
+    o = *out;
+    TORCH_CHECK(o.is_cuda() && o.device() == qkv.device() &&
+                    o.is_contiguous() &&
+                    o.scalar_type() == qkv.scalar_type() && o.dim() == 2 &&
+                    o.size(0) == S && o.size(1) == H,
+                "flash_attn_tilepack_infer: out must be contiguous [T, H] of "
+                "qkv's dtype and device");
+  } else {
+    o = torch::empty({S, H}, qkv.options());
+  }
+  const dim3 grid(M, nh);
+  // bf16 or fp16: check_fa_varlen_args
+  if (qkv.scalar_type() == torch::kBFloat16)
+    fa_infer_launch<__hip_bfloat16, bf16x8>(qkv, plan, o, grid, max_seqlen,
+                                            nh, scale);
+  else
+    fa_infer_launch<__half, f16x8>(qkv, plan, o, grid, max_seqlen, nh, scale);
+  return o;
 }

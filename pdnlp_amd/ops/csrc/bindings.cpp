@@ -123,6 +123,12 @@ torch::Tensor flash_attn_tilepack_bwd(torch::Tensor dout, torch::Tensor qkv,
                                       torch::Tensor plan, long max_seqlen,
                                       long nh, double scale, double p,
                                       torch::Tensor seed_buf, long salt);
+torch::Tensor flash_attn_tilepack_infer(torch::Tensor qkv, torch::Tensor plan,
+                                        long max_seqlen, long nh, double scale,
+                                        std::optional<torch::Tensor> out);
+torch::Tensor bias_dropout_residual_ln_infer(
+    torch::Tensor y, torch::Tensor bias, torch::Tensor res, torch::Tensor lnw,
+    torch::Tensor lnb, double eps);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_fwd", &layernorm_fwd);
@@ -180,4 +186,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn_tilepack_plan", &flash_attn_tilepack_plan);
   m.def("flash_attn_tilepack_fwd", &flash_attn_tilepack_fwd);
   m.def("flash_attn_tilepack_bwd", &flash_attn_tilepack_bwd);
+  // forward-only (serving) forms: no lse/xsum/mask/mean/rstd, no fill launch
+  m.def("flash_attn_tilepack_infer", &flash_attn_tilepack_infer,
+        py::arg("qkv"), py::arg("plan"), py::arg("max_seqlen"), py::arg("nh"),
+        py::arg("scale"), py::arg("out") = py::none());
+  m.def("bias_dropout_residual_ln_infer", &bias_dropout_residual_ln_infer);
 }

@@ -22,7 +22,10 @@ namespace {
 // seed is read from DEVICE memory (seed_base) + a per-call-site salt so the
 // dropout mask changes across hipGraph replays (the host updates *seed_base
 // between replays; a kernel-arg seed would be frozen into the graph).
-template <typename T, bool DROP>
+// INFER (serving, DROP = false): only out is produced. xsum, mask, mean and
+// rstd are neither allocated nor stored; the second pass forms xsum again
+// from its inputs (the same two rounded adds) instead of reading it back.
+template <typename T, bool DROP, bool INFER = false>
 __global__ __launch_bounds__(256)
 void bdrl_fwd_kernel(const T* __restrict__ y, const T* __restrict__ bias,
                      const T* __restrict__ res, const T* __restrict__ lnw,
@@ -33,13 +36,14 @@ void bdrl_fwd_kernel(const T* __restrict__ y, const T* __restrict__ bias,
                      float* __restrict__ rstd_out, int H, float p, float eps,
                      const unsigned long long* __restrict__ seed_base,
                      unsigned long long salt, long R) {
+  static_assert(!INFER || !DROP, "INFER is a dropout-free form");
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= R) return;
   const unsigned long long seed = (DROP ? *seed_base : 0ull) + salt;
   const int lane = threadIdx.x & (WAVE - 1);
   const T* yr = y + row * H;
   const T* rr = res + row * H;
-  T* xr = xsum + row * H;
+  T* xr = INFER ? nullptr : xsum + row * H;
   T* outr = out + row * H;
   const float inv_keep = 1.f / (1.f - p);
 
@@ -74,17 +78,29 @@ void bdrl_fwd_kernel(const T* __restrict__ y, const T* __restrict__ bias,
       sum += hs;
       sumsq += hs * hs;
     }
-    st4(xr + c, xv);
+    if (!INFER) st4(xr + c, xv);
     if (DROP) *reinterpret_cast<uchar4*>(mask_out + row * H + c) = mv;
   }
   float md, mean, rstd;  // md = mean - shift
   shifted_stats(wave_sum(sum), wave_sum(sumsq), shift, H, eps, md, mean, rstd);
-  if (lane == 0) {
+  if (!INFER && lane == 0) {
     mean_out[row] = mean;
     rstd_out[row] = rstd;
   }
   for (int c = lane * 4; c < H; c += WAVE * 4) {
-    const v4_t<T> xv = ld4(xr + c), wv = ld4(lnw + c), bv = ld4(lnb + c);
+    const v4_t<T> wv = ld4(lnw + c), bv = ld4(lnb + c);
+    v4_t<T> xv;
+    if constexpr (INFER) {
+      const v4_t<T> yv = ld4(yr + c), pv = ld4(bias + c), rv = ld4(rr + c);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float h = elem<T>(yv, j) + elem<T>(pv, j);
+        h += elem<T>(rv, j);
+        set_elem<T>(xv, j, h);
+      }
+    } else {
+      xv = ld4(xr + c);
+    }
     v4_t<T> ov;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -255,7 +271,8 @@ __device__ __forceinline__ __half mul_round_once(float a, float b) {
   return __ushort_as_half((unsigned short)r);
 }
 
-template <typename T, bool DROP, int NV>
+// INFER (serving, DROP = false): as in bdrl_fwd_kernel, only out is stored.
+template <typename T, bool DROP, int NV, bool INFER = false>
 __global__ __launch_bounds__(256)
 void bdrl_fwd1_kernel(const T* __restrict__ y, const T* __restrict__ bias,
                       const T* __restrict__ res, const T* __restrict__ lnw,
@@ -267,6 +284,7 @@ void bdrl_fwd1_kernel(const T* __restrict__ y, const T* __restrict__ bias,
                       const unsigned long long* __restrict__ seed_base,
                       unsigned long long salt, long R) {
 #pragma clang fp contract(off)  // see the note above: fusion is spelled out
+  static_assert(!INFER || !DROP, "INFER is a dropout-free form");
   constexpr int H = NV * 256;
   const long nwaves = (long)gridDim.x * 4;
   long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -331,13 +349,13 @@ void bdrl_fwd1_kernel(const T* __restrict__ y, const T* __restrict__ bias,
         sum += hs;
         sumsq += hs * hs;
       }
-      st4(xsum + row * H + c, xv[k]);
+      if (!INFER) st4(xsum + row * H + c, xv[k]);
       if (DROP) *reinterpret_cast<uchar4*>(mask_out + row * H + c) = mv;
     }
     float md, mean, rstd;
     shifted_stats(wave_sum(sum), wave_sum(sumsq), shift, H, eps, md, mean,
                   rstd);
-    if (lane == 0) {
+    if (!INFER && lane == 0) {
       mean_out[row] = mean;
       rstd_out[row] = rstd;
     }
@@ -623,6 +641,64 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_fwd(
     });
   });
   return {out, xsum, mask, mean, rstd};
+}
+
+// Serving form of bias_dropout_residual_ln_fwd at p = 0: the INFER
+// instantiations, routed as that function routes. Returns out alone, with
+// the bits of that function's out.
+torch::Tensor bias_dropout_residual_ln_infer(
+    torch::Tensor y, torch::Tensor bias, torch::Tensor res, torch::Tensor lnw,
+    torch::Tensor lnb, double eps) {
+  const int H = y.size(-1);
+  const long R = y.numel() / H;
+  TORCH_CHECK(H % 4 == 0, "bdrl: hidden size must be a multiple of 4");
+  TORCH_CHECK(y.is_cuda() && y.is_contiguous() && res.is_contiguous() &&
+                  res.numel() == y.numel() &&
+                  res.scalar_type() == y.scalar_type() &&
+                  bias.numel() == H && lnw.numel() == H && lnb.numel() == H &&
+                  bias.scalar_type() == y.scalar_type() &&
+                  lnw.scalar_type() == y.scalar_type() &&
+                  lnb.scalar_type() == y.scalar_type(),
+              "bdrl_infer: y/residual contiguous [.., H], bias/ln_w/ln_b [H], "
+              "one dtype");
+  auto out = torch::empty_like(y);
+  if (R == 0) return out;
+  auto stream = at::hip::getCurrentHIPStream();
+  const long grid = (R + 3) / 4;
+  if (H % 256 == 0 && H <= 1024 && !bdrl_two_pass()) {
+    const long cus = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+    const long grid1 = std::min(grid, 8 * cus);
+    DISPATCH_FLOAT_TYPES(y.scalar_type(), "bdrl_infer", [&] {
+      dispatch_nv(H / 256, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        hipLaunchKernelGGL((bdrl_fwd1_kernel<scalar_t, false, NV, true>),
+                           dim3(grid1), dim3(256), 0, stream,
+                           (const scalar_t*)y.data_ptr(),
+                           (const scalar_t*)bias.data_ptr(),
+                           (const scalar_t*)res.data_ptr(),
+                           (const scalar_t*)lnw.data_ptr(),
+                           (const scalar_t*)lnb.data_ptr(),
+                           (scalar_t*)out.data_ptr(), (scalar_t*)nullptr,
+                           (unsigned char*)nullptr, (float*)nullptr,
+                           (float*)nullptr, 0.f, (float)eps,
+                           (const unsigned long long*)nullptr, 0ull, R);
+      });
+    });
+    return out;
+  }
+  DISPATCH_FLOAT_TYPES(y.scalar_type(), "bdrl_infer", [&] {
+    hipLaunchKernelGGL((bdrl_fwd_kernel<scalar_t, false, true>), dim3(grid),
+                       dim3(256), 0, stream, (const scalar_t*)y.data_ptr(),
+                       (const scalar_t*)bias.data_ptr(),
+                       (const scalar_t*)res.data_ptr(),
+                       (const scalar_t*)lnw.data_ptr(),
+                       (const scalar_t*)lnb.data_ptr(),
+                       (scalar_t*)out.data_ptr(), (scalar_t*)nullptr,
+                       (unsigned char*)nullptr, (float*)nullptr,
+                       (float*)nullptr, H, 0.f, (float)eps,
+                       (const unsigned long long*)nullptr, 0ull, R);
+  });
+  return out;
 }
 
 namespace {

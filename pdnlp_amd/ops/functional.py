@@ -8,8 +8,10 @@ tested against). Kernel inventory mirrors SURVEY.md §2.3 K1-K16.
 
 from __future__ import annotations
 
+import contextlib
 import math
 import os
+import threading
 from typing import Optional
 
 import torch
@@ -17,6 +19,35 @@ import torch.nn.functional as F
 
 from . import hip_enabled, ext
 from .tile_plan import AttnTilePlan, plan_from_reference, plan_views
+
+
+# --------------------------------------------------------------------------
+# Forward-only (serving) kernel selection
+# --------------------------------------------------------------------------
+
+_infer_state = threading.local()
+
+
+@contextlib.contextmanager
+def inference_kernels(enabled: bool = True):
+    """Inside this context, with autograd off, tile-packed attention and the
+    fused bias+residual+LN epilogue run their forward-only instantiations
+    (``flash_attn_tilepack_infer``, ``bias_dropout_residual_ln_infer``):
+    same output bits, but nothing is stored that only a backward reads
+    (lse, xsum, mean, rstd) and the attention output needs no fill launch.
+    The flag is thread-local and never set implicitly; outside the context,
+    or with autograd on, every op runs as before."""
+    prev = getattr(_infer_state, "on", False)
+    _infer_state.on = bool(enabled)
+    try:
+        yield
+    finally:
+        _infer_state.on = prev
+
+
+def _infer_active() -> bool:
+    return getattr(_infer_state, "on", False) \
+        and not torch.is_grad_enabled()
 
 
 # --------------------------------------------------------------------------
@@ -589,6 +620,10 @@ def attention_varlen(qkv: torch.Tensor, cu_seqlens: torch.Tensor,
     if hip_enabled(qkv) and hd == 64 and T % 64 == 0 \
             and qkv.dtype in (torch.bfloat16, torch.float16):
         if plan is not None:
+            if p_eff == 0.0 and _infer_active():
+                return ext().flash_attn_tilepack_infer(
+                    qkv.contiguous(), plan.buf, int(max_seqlen), num_heads,
+                    1.0 / math.sqrt(hd))
             return _FlashAttnTilePackFn.apply(
                 qkv.contiguous(), plan.buf, int(max_seqlen), num_heads,
                 1.0 / math.sqrt(hd), p_eff)
@@ -685,6 +720,9 @@ def bias_dropout_residual_layernorm(
     """out = LN(dropout(y + bias) + residual) — the fused epilogue after the
     attention-output and FFN-down projections."""
     if hip_enabled(y) and y.shape[-1] % 256 == 0 and y.shape[-1] <= 1024:
+        if not (p > 0.0 and training) and _infer_active():
+            return ext().bias_dropout_residual_ln_infer(
+                y.contiguous(), bias, residual.contiguous(), ln_w, ln_b, eps)
         return _BiasDropResLNFn.apply(y, bias, residual, ln_w, ln_b, p,
                                       training, eps, True)
     h = y + bias
@@ -714,6 +752,9 @@ def linear_bias_dropout_residual_layernorm(
             and not dw_stream.enabled() \
             and _gemm_shape_ok(x, w) and rows % 64 == 0:
         proj = _LinearDeferredBiasHipFn.apply(x, w, b)
+        if not (p > 0.0 and training) and _infer_active():
+            return ext().bias_dropout_residual_ln_infer(
+                proj.contiguous(), b, residual.contiguous(), ln_w, ln_b, eps)
         return _BiasDropResLNFn.apply(
             proj, b.detach(), residual, ln_w, ln_b, p, training, eps, False)
     return bias_dropout_residual_layernorm(

@@ -41,15 +41,20 @@ def main():
     p.add_argument("--label", type=int, default=3,
                    help="pick a random dataset sample with this label")
     p.add_argument("--ckpt", action="append", default=None)
-    p.add_argument("--engine", choices=["eager", "graphed"],
+    p.add_argument("--engine", choices=["eager", "graphed", "packed"],
                    default="eager",
                    help="graphed = hipGraph-captured serving forward "
-                        "(pdnlp_amd.engine.InferenceEngine)")
+                        "(pdnlp_amd.engine.InferenceEngine); packed = its "
+                        "padding-free form (packed token stream, one graph "
+                        "per bucketed size, forward-only kernels)")
     ns, rest = p.parse_known_args()
     args = Args().apply_cli(rest)
     set_seed(args.seed)
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
-    tokenizer = build_tokenizer(args.model_path)
+    # the vocabulary of the model in use, as the training CLI picks it
+    from pdnlp_amd.cli import _VOCAB
+    tokenizer = build_tokenizer(args.model_path,
+                                vocab_size=_VOCAB.get(args.model, 21128))
 
     if ns.text is not None:
         text, true_label = ns.text, None
@@ -71,7 +76,16 @@ def main():
         model = build_model(args.model, model_path=args.model_path)
         if c is not None:
             load_checkpoint(model, c)
-        if ns.engine == "graphed":
+        if ns.engine == "packed":
+            from pdnlp_amd.engine import InferenceEngine
+            if torch.cuda.is_available():
+                model = model.to(torch.bfloat16)
+            eng = InferenceEngine(model, tokenizer, device=str(device),
+                                  max_seq_len=args.max_seq_len, packed=True)
+            pred = eng.predict([text])[0]
+            print(f"{c or '<random-init>'} → predicted: {LABELS[pred]} "
+                  f"(packed, {eng.graph_stats})")
+        elif ns.engine == "graphed":
             from pdnlp_amd.engine import InferenceEngine
             if torch.cuda.is_available():
                 model = model.to(torch.bfloat16)

@@ -9,7 +9,10 @@ packed rows (tools/bench_unpad.py's seeded lognormal lengths, batched by
 TokenBudgetBatchSampler), BERT-base heads, bf16, random data. Device events
 around ``--iters`` launches; the modes alternate for ``--rounds`` rounds in
 one process and the per-round means are reported with their range. The plan
-kernel (once per model forward, not per layer) is timed on its own.
+kernel (once per model forward, not per layer) is timed on its own. The
+serving pair rides along: the tile-packed forward at p = 0 (zero-fill launch,
+kernel, lse) next to ``flash_attn_tilepack_infer``, which replaces it under
+``ops.inference_kernels()``.
 """
 import argparse
 import json
@@ -102,6 +105,10 @@ def packed(a):
         "tile_packed_bwd": lambda: e.flash_attn_tilepack_bwd(
             do, qkv, o_tp, lse_tp, plan, mx, nh, sc, p, seed, 1),
         "plan": lambda: e.flash_attn_tilepack_plan(cu_t, T),
+        "tile_packed_fwd_p0": lambda: e.flash_attn_tilepack_fwd(
+            qkv, plan, mx, nh, sc, 0.0, torch.Tensor(), 0),
+        "tile_packed_infer": lambda: e.flash_attn_tilepack_infer(
+            qkv, plan, mx, nh, sc),
     }
     for fn in fns.values():
         for _ in range(10):
@@ -118,6 +125,10 @@ def packed(a):
         ps, tp = us[f"per_sequence_{d}"], us[f"tile_packed_{d}"]
         print(f"{d}: ranges disjoint in favour of tile-packed: "
               f"{max(tp) < min(ps)}; of per-sequence: {max(ps) < min(tp)}")
+    f0, inf = us["tile_packed_fwd_p0"], us["tile_packed_infer"]
+    print(f"serving fwd: ranges disjoint in favour of infer: "
+          f"{max(inf) < min(f0)}; of the training forward: "
+          f"{max(f0) < min(inf)}")
     print(json.dumps({"metric": "bench_attention_packed", "rows": T,
                       "dropout": p, "sentences": len(bl),
                       "live_blocks_per_head": {"per_sequence": live,

@@ -2,6 +2,8 @@
 """Per-call time of the fused bias + dropout + residual + LayerNorm epilogue.
 
     python tools/bench_bdrl.py [--rounds 5] [--calls 48] [--shape R H ...]
+    python tools/bench_bdrl.py --infer     # serving: forward at p = 0 next
+                                           # to bias_dropout_residual_ln_infer
 
 Forward (``bias_dropout_residual_ln_fwd``) and backward
 (``bias_dropout_residual_ln_bwd_nodb``, the variant the flagship step runs)
@@ -89,6 +91,64 @@ def build_graphs(e, R, H, env, calls):
     return graphs, keep
 
 
+def build_infer_graphs(e, R, H, calls):
+    """{"fwd_p0", "infer"}: the training forward at p = 0 and the forward-only
+    op that replaces it under ``ops.inference_kernels()``, same inputs"""
+    g = torch.Generator(device=DEV).manual_seed(R + H)
+    rnd = lambda *s: torch.randn(*s, device=DEV, generator=g).to(torch.bfloat16)
+    bias, lnw, lnb = rnd(H), rnd(H), rnd(H)
+    sets = [(rnd(R, H), rnd(R, H)) for _ in range(SETS)]
+    calls_of = {
+        "fwd_p0": lambda y, res: e.bias_dropout_residual_ln_fwd(
+            y, bias, res, lnw, lnb, 0.0, EPS, torch.Tensor(), 0),
+        "infer": lambda y, res: e.bias_dropout_residual_ln_infer(
+            y, bias, res, lnw, lnb, EPS),
+    }
+    for fn in calls_of.values():
+        fn(*sets[0])
+    torch.cuda.synchronize()
+    graphs, keep = {}, []
+    for name, fn in calls_of.items():
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            for i in range(calls):
+                keep.append(fn(*sets[i % SETS]))
+        graphs[name] = graph
+    return graphs, keep
+
+
+def bench_infer(rounds, calls, shapes):
+    e = ops.ext()
+    assert e is not None, "the HIP extension is not built"
+    lines = []
+    for R, H in shapes:
+        graphs, keep = build_infer_graphs(e, R, H, calls)
+        for graph in graphs.values():             # warm-up
+            time_graph(graph, calls)
+        us = {name: [] for name in graphs}
+        for _ in range(rounds):
+            for name, graph in graphs.items():
+                us[name].append(time_graph(graph, calls))
+        t = R * H * 2
+        nbytes = {"fwd_p0": 4 * t, "infer": 3 * t}   # y, res in; (xsum,) out
+        for name, v in us.items():
+            med = statistics.median(v)
+            lines.append({"shape": [R, H], "path": name,
+                          "us_per_call": [round(u, 2) for u in v],
+                          "median_us": round(med, 2),
+                          "unique_MB": round(nbytes[name] / 1e6, 1)})
+            print(f"[{R}, {H}] {name:7s}: {min(v):6.2f} .. {max(v):6.2f} "
+                  f"us/call, median {med:6.2f}, "
+                  f"{nbytes[name] / 1e6:.1f} MB unique", flush=True)
+        print(f"[{R}, {H}] ranges disjoint in favour of infer: "
+              f"{max(us['infer']) < min(us['fwd_p0'])}; of the training "
+              f"forward: {max(us['fwd_p0']) < min(us['infer'])}")
+        del graphs, keep
+        torch.cuda.empty_cache()
+    print(json.dumps(lines))
+    return lines
+
+
 def time_graph(graph, calls):
     t0 = torch.cuda.Event(enable_timing=True)
     t1 = torch.cuda.Event(enable_timing=True)
@@ -150,7 +210,14 @@ def main():
                     metavar=("R", "H"),
                     help="time this [R, H] instead of the two default "
                          "shapes (repeatable); H a multiple of 256, <= 1024")
+    ap.add_argument("--infer", action="store_true",
+                    help="time the forward at p = 0 next to the forward-only "
+                         "op of serving, at [4096, 768] unless --shape")
     a = ap.parse_args()
+    if a.infer:
+        bench_infer(a.rounds, a.calls,
+                    [tuple(s) for s in a.shape] if a.shape else SHAPES[:1])
+        return
     shapes = [tuple(s) for s in a.shape] if a.shape else SHAPES
     report(bench({"onepass": {}, "2pass": {"PDNLP_BDRL_2PASS": "1"}},
                  a.rounds, a.calls, shapes))
