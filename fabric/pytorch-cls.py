@@ -32,6 +32,10 @@ def main():
         raise SystemExit("--attn-tile-pack is not supported by this "
                          "entrypoint (it needs --unpad true); use "
                          "single-gpu-cls.py or a multi-gpu-*-cls.py script")
+    if args.cls_only_last_layer:
+        raise SystemExit("--cls-only-last-layer is not supported by this "
+                         "entrypoint (it needs --unpad true); use "
+                         "single-gpu-cls.py or a multi-gpu-*-cls.py script")
     if args.unpad:
         raise SystemExit("--unpad true is not supported by this entrypoint "
                          "(its own loop feeds padded [B, S] batches); use "

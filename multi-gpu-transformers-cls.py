@@ -57,6 +57,7 @@ def main():
     hf_args.unpad = base.unpad
     hf_args.max_tokens = base.max_tokens
     hf_args.attn_tile_pack = base.attn_tile_pack
+    hf_args.cls_only_last_layer = base.cls_only_last_layer
     trainer = HFStyleTrainer(model, hf_args, train_dataset=train_ds,
                              eval_dataset=dev_ds, data_collator=collate,
                              compute_metrics=compute_metrics)

@@ -23,7 +23,7 @@ from .data import (SEQ_MULTIPLE, ClsDataset, Collate, DistributedSampler,
                    build_tokenizer, load_data, sequence_lengths,
                    train_dev_split)
 from .engine.trainer import (build_training, check_attn_tile_pack,
-                             check_token_budget)
+                             check_cls_only_last_layer, check_token_budget)
 from .parallel.bootstrap import cleanup, init_distributed, spawn
 from .utils import set_seed
 from .utils.checkpoint import load_checkpoint
@@ -67,6 +67,7 @@ def token_budget_loader(args: Args, dataset, collate: Collate,
 def build_dataloaders(args: Args, world_size: int, rank: int):
     check_token_budget(args)
     check_attn_tile_pack(args)
+    check_cls_only_last_layer(args)
     vocab_size = _VOCAB.get(getattr(args, "model", "bert-base"), 21128)
     if os.path.isfile(args.data_path):
         data = load_data(args.data_path, limit=args.data_limit)

@@ -35,6 +35,9 @@ class BertConfig:
     model_type: str = "bert"           # "bert" | "roberta"
     attn_tile_pack: bool = False       # packed batches: several short
                                        # sequences per 64-row attention tile
+    cls_only_last_layer: bool = False  # packed batches: the last encoder
+                                       # layer runs on the first-token rows
+                                       # alone after its QKV projection
 
     @property
     def head_dim(self) -> int:
@@ -120,6 +123,9 @@ class Args:
     attn_tile_pack: bool = False       # with unpad: tile-packed attention,
                                        # several whole short sequences per
                                        # 64-row tile (models' attn_tile_pack)
+    cls_only_last_layer: bool = False  # with unpad: the last encoder layer
+                                       # computes the first-token rows only
+                                       # (models' cls_only_last_layer)
 
     # optimization
     train_batch_size: int = 32         # per GPU

@@ -50,6 +50,8 @@ class TrainingArguments:
                           # many packed rows (per_device_train_batch_size
                           # is then not used); 0 = off
     attn_tile_pack: bool = False  # with unpad: tile-packed attention
+    cls_only_last_layer: bool = False  # with unpad: last encoder layer on
+                                       # the first-token rows only
     # global-norm gradient clipping, 0 = off. HF's own default is 1.0 (so
     # the reference's transformers run clips); set 1.0 to reproduce it.
     max_grad_norm: float = 0.0
@@ -83,6 +85,7 @@ class HFStyleTrainer:
         eargs.unpad = args.unpad
         eargs.max_tokens = args.max_tokens
         eargs.attn_tile_pack = args.attn_tile_pack
+        eargs.cls_only_last_layer = args.cls_only_last_layer
         eargs.max_grad_norm = args.max_grad_norm
         eargs.output_dir = args.output_dir
         eargs.ckpt_path = os.path.join(args.output_dir, "best_model.pt")

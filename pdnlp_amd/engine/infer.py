@@ -206,6 +206,8 @@ class InferenceEngine:
     of any size is cut into ranges of at most ``max_tokens`` real tokens and
     ``max_seqs`` texts; at most ``max_graphs`` keys get a graph, further
     keys run eager; ``infer_kernels`` selects the forward-only kernels.
+    ``cls_only_last_layer=True`` (packed only) also sets that config field
+    on the copy: the last encoder layer computes the first-token rows only.
     ``graph_stats`` counts packed forwards: ``captured`` graphs, and each
     forward under ``replayed`` or ``eager`` (the forward that triggers a
     capture is replayed from the new graph and counts as replayed; the
@@ -217,10 +219,15 @@ class InferenceEngine:
                  max_seq_len: int = 128, use_graph: bool = True,
                  packed: bool = False, max_tokens: int = 4096,
                  max_seqs: int = 1024, max_graphs: int = 32,
-                 infer_kernels: bool = True):
+                 infer_kernels: bool = True,
+                 cls_only_last_layer: bool = False):
         self.device = torch.device(
             device or ("cuda" if torch.cuda.is_available() else "cpu"))
         self.packed = bool(packed)
+        if cls_only_last_layer and not self.packed:
+            raise ValueError("InferenceEngine: cls_only_last_layer needs "
+                             "packed=True (padded batches have no packed "
+                             "stream to take the first-token rows from)")
         if self.packed:
             if max_tokens % 64 or max_tokens < max_seq_len:
                 raise ValueError("InferenceEngine: max_tokens must be a "
@@ -233,7 +240,9 @@ class InferenceEngine:
             # the engine's own copy: the caller's model keeps its config
             model = copy.deepcopy(model)
             old = model.config
-            cfg = dataclasses.replace(old, attn_tile_pack=True)
+            cfg = dataclasses.replace(
+                old, attn_tile_pack=True,
+                cls_only_last_layer=bool(cls_only_last_layer))
             for m in model.modules():
                 for name in ("cfg", "config"):
                     if getattr(m, name, None) is old:

@@ -145,6 +145,7 @@ class Trainer:
         # (HFStyleTrainer uses it for checkpoint-N dirs)
         self.step_callback = None
         apply_attn_tile_pack(args, model)
+        apply_cls_only_last_layer(args, model)
 
     # ------------------------------------------------------------------
     def on_step(self, batch):
@@ -728,6 +729,30 @@ def apply_attn_tile_pack(args, model) -> None:
         cfg.attn_tile_pack = True
 
 
+def check_cls_only_last_layer(args) -> None:
+    """Reject ``--cls-only-last-layer true`` without the packed stream."""
+    if getattr(args, "cls_only_last_layer", False) \
+            and not getattr(args, "unpad", False):
+        raise ValueError(
+            "--cls-only-last-layer needs --unpad true: it runs the last "
+            "encoder layer on the first-token rows of the packed stream, "
+            "which padded [B, S] batches do not have.")
+
+
+def apply_cls_only_last_layer(args, model) -> None:
+    """Hand ``args.cls_only_last_layer`` to the (unwrapped) model's config.
+    The model decides per forward from (T, B) alone, so the batch dict, the
+    graph key and the strategy wrappers know nothing about it."""
+    check_cls_only_last_layer(args)
+    if getattr(args, "cls_only_last_layer", False):
+        inner = getattr(model, "module", model)
+        cfg = getattr(inner, "cfg", None)
+        if cfg is None or not hasattr(cfg, "cls_only_last_layer"):
+            raise ValueError("--cls-only-last-layer: the model has no "
+                             "cls_only_last_layer config field")
+        cfg.cls_only_last_layer = True
+
+
 def build_training(args, model=None, label_key: str = "label"):
     """Assemble (model, optimizer, scaler, trainer) for a strategy mode.
 
@@ -750,6 +775,7 @@ def build_training(args, model=None, label_key: str = "label"):
             "stream does not have. Use strategy=ddp (one process per GPU).")
     check_token_budget(args)
     check_attn_tile_pack(args)
+    check_cls_only_last_layer(args)
     ndev = max(torch.cuda.device_count(), 1)
     device = torch.device(f"cuda:{args.local_rank % ndev}"
                           if torch.cuda.is_available() else "cpu")

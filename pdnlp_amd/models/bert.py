@@ -159,7 +159,12 @@ class BertLayer(nn.Module):
     def forward(self, h: torch.Tensor, attn_mask: Optional[torch.Tensor],
                 training: bool, cu_seqlens: Optional[torch.Tensor] = None,
                 max_seqlen: Optional[int] = None,
-                attn_plan=None) -> torch.Tensor:
+                attn_plan=None,
+                cls_rows: Optional[int] = None) -> torch.Tensor:
+        """``cls_rows`` (packed streams only; the last layer under
+        ``cfg.cls_only_last_layer``): after the QKV projection over all T
+        rows, everything runs on the ``cls_rows`` first-token rows alone and
+        the layer returns [1, cls_rows, H] in place of [1, T, H]."""
         cfg = self.cfg
         nh = cfg.num_attention_heads
         a = self.attention.self
@@ -169,7 +174,16 @@ class BertLayer(nn.Module):
         # node so the residual-grad fan-in add fuses into the dX GEMM
         # epilogue (ops/functional.py _LinearForkHipFn)
         qkv, h_res = ops.linear_fork(h, a.qkv_weight, a.qkv_bias)
-        if cu_seqlens is not None:
+        if cls_rows is not None:
+            # K and V need every row, the query side only the first token
+            # of each sequence: one attention row per sequence, and the
+            # residual gathered from the same rows. The gather's backward
+            # scatters into the dpass of the projection node above.
+            ctx = ops.cls_attention(
+                qkv[0], cu_seqlens, cls_rows, max_seqlen, nh,
+                cfg.attention_probs_dropout_prob, training).unsqueeze(0)
+            h_res = _first_token_rows(h_res, cu_seqlens, cls_rows)
+        elif cu_seqlens is not None:
             # packed stream h [1, T, H]: sequence-boundary-aware attention
             ctx = ops.attention_varlen(
                 qkv[0], cu_seqlens, max_seqlen, nh,
@@ -226,9 +240,14 @@ class BertModel(nn.Module):
         (``cu_seqlens`` given): ``input_ids``/``token_type_ids``/
         ``position_ids`` are the 1-D token stream [T] of ``pack_batch``,
         ``attention_mask`` is ignored, and the hidden states come back as
-        the packed [1, T, H] stream."""
+        the packed [1, T, H] stream. With ``cfg.cls_only_last_layer`` (and
+        ``cls_only_rows`` not None) the last layer computes the first-token
+        rows only, and the hidden states come back as that first-token
+        stream [1, R, H] instead: row i < B belongs to sequence i, rows of
+        empty sequences and rows B..R hold finite values nothing reads."""
         training = self.training
         attn_plan = None
+        cls_rows = None
         if cu_seqlens is not None:
             assert input_ids.dim() == 1 and position_ids is not None \
                 and max_seqlen is not None, \
@@ -243,6 +262,8 @@ class BertModel(nn.Module):
             if self.cfg.attn_tile_pack:
                 attn_plan = ops.varlen_attention_plan(cu_seqlens,
                                                       input_ids.numel())
+            cls_rows = cls_only_rows(self.cfg, input_ids.numel(),
+                                     cu_seqlens.numel() - 1)
         else:
             if attention_mask is None:
                 attention_mask = torch.ones_like(input_ids)
@@ -252,15 +273,20 @@ class BertModel(nn.Module):
             addmask = (1.0 - attention_mask[:, None, None, :].to(dtype)) \
                 * -10000.0
             h = self.embeddings(input_ids, token_type_ids, training)
-        for layer in self.encoder.layer:
+        last = len(self.encoder.layer) - 1
+        for n, layer in enumerate(self.encoder.layer):
+            rows = cls_rows if n == last else None
             if self._grad_ckpt and training:
                 h = _checkpoint_layer(layer, h, addmask, training,
                                       self._ckpt_cpu_offload, cu_seqlens,
-                                      max_seqlen, attn_plan)
+                                      max_seqlen, attn_plan, rows)
             else:
                 h = layer(h, addmask, training, cu_seqlens, max_seqlen,
-                          attn_plan)
-        if cu_seqlens is not None:
+                          attn_plan, rows)
+        if cls_rows is not None:
+            # h is already the first-token stream: no second gather
+            cls = h[0, :cu_seqlens.numel() - 1]
+        elif cu_seqlens is not None:
             cls = _packed_cls(h, cu_seqlens)
         else:
             cls = h[:, 0]
@@ -287,6 +313,29 @@ def _packed_cls(h, cu_seqlens):
     return h[0].index_select(0, idx)
 
 
+def cls_only_rows(cfg, total_rows: int, num_seqs: int) -> Optional[int]:
+    """Row count R = ceil64(B) of the last layer's first-token stream under
+    ``cfg.cls_only_last_layer``, or None when the layer runs as usual: the
+    option is off, or R >= T and there is nothing to save (one text in a
+    64-row stream). Host integers only and a function of (T, B), so every
+    batch of a graph key decides the same way. A multiple of 64 keeps the
+    first-party GEMMs and the deferred-bias path engaged."""
+    if not getattr(cfg, "cls_only_last_layer", False):
+        return None
+    rows = -(-int(num_seqs) // 64) * 64
+    return rows if rows < int(total_rows) else None
+
+
+def _first_token_rows(h, cu_seqlens, rows: int):
+    """[1, rows, H] first-token rows of a packed stream h [1, T, H], with no
+    host sync. Clamped as ``_packed_cls`` clamps; the rows past the batch
+    gather row 0. Those and the rows of empty sequences are real, finite
+    rows whose outputs nothing reads, so their gradients are exactly zero."""
+    idx = torch.nn.functional.pad(cu_seqlens[:-1].long(),
+                                  (0, rows - (cu_seqlens.numel() - 1)))
+    return h[0].index_select(0, idx.clamp(max=h.shape[1] - 1)).unsqueeze(0)
+
+
 def _cls_loss(logits, labels, cu_seqlens):
     """Packed batches may carry empty sequences labelled -100; padded
     batches take the plain mean."""
@@ -298,7 +347,8 @@ def _cls_loss(logits, labels, cu_seqlens):
 
 
 def _checkpoint_layer(layer, h, mask, training, cpu_offload,
-                      cu_seqlens=None, max_seqlen=None, attn_plan=None):
+                      cu_seqlens=None, max_seqlen=None, attn_plan=None,
+                      cls_rows=None):
     """Activation checkpointing (deepspeed-capability equivalent,
     reference config: multi-gpu-deepspeed-cls.py:240-244), optional CPU
     offload of the saved input over PCIe."""
@@ -307,9 +357,10 @@ def _checkpoint_layer(layer, h, mask, training, cpu_offload,
         ctx = torch.autograd.graph.save_on_cpu(pin_memory=True)
         with ctx:
             return cp.checkpoint(layer, h, mask, training, cu_seqlens,
-                                 max_seqlen, attn_plan, use_reentrant=False)
+                                 max_seqlen, attn_plan, cls_rows,
+                                 use_reentrant=False)
     return cp.checkpoint(layer, h, mask, training, cu_seqlens, max_seqlen,
-                         attn_plan, use_reentrant=False)
+                         attn_plan, cls_rows, use_reentrant=False)
 
 
 class BertForSequenceClassification(nn.Module):
@@ -364,8 +415,13 @@ class RobertaForSequenceClassification(nn.Module):
                 position_ids=None):
         h, _ = self.roberta(input_ids, attention_mask, token_type_ids,
                             cu_seqlens, max_seqlen, position_ids)
-        cls = _packed_cls(h, cu_seqlens) if cu_seqlens is not None \
-            else h[:, 0]
+        if cu_seqlens is None:
+            cls = h[:, 0]
+        elif cls_only_rows(self.cfg, input_ids.numel(),
+                           cu_seqlens.numel() - 1) is not None:
+            cls = h[0, :cu_seqlens.numel() - 1]  # h: first-token stream
+        else:
+            cls = _packed_cls(h, cu_seqlens)
         x = ops.dropout(cls, self.cfg.hidden_dropout_prob, self.training)
         x = ops.linear(x, self.classifier.dense.weight,
                        self.classifier.dense.bias, act="tanh")

@@ -80,6 +80,7 @@ from .functional import (  # noqa: F401,E402
     attention,
     attention_packed,
     attention_varlen,
+    cls_attention,
     varlen_attention_plan,
     masked_softmax,
     cross_entropy,

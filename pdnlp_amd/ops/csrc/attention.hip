@@ -45,6 +45,7 @@
 
 #include <optional>
 
+#include "attn_common.h"  // drop_idx, varlen_len
 #include "gemm_common.h"  // vector typedefs, mfma16
 
 namespace {
@@ -164,24 +165,8 @@ __device__ __forceinline__ float qsum(float x) {
   return x;
 }
 
-// dropout counter for probability (qrow, key): qrow is the head-major row
-// (padded: bh*S + row; VARLEN: h*T + packed row), key the key index inside
-// the sequence. Identical in forward, dQ and dK/dV. VARLEN strides rows by
-// the 1024 key cap instead of S, so nh*T <= 2^22 (host-checked) cannot wrap.
-template <bool VARLEN>
-__device__ __forceinline__ unsigned int drop_idx(unsigned int qrow,
-                                                 unsigned int key, int S) {
-  return VARLEN ? (qrow << 10) + key : qrow * S + key;
-}
-
-// VARLEN sequence length of batch entry b, clamped so that a bad cu_seqlens
-// can neither leave the [T] stream nor the 1024-entry LDS rows
-__device__ __forceinline__ int varlen_len(const int* cu_seqlens, long b,
-                                          long row0, int T) {
-  const long len = cu_seqlens[b + 1] - row0;
-  const long cap = T - row0 < 1024 ? T - row0 : 1024;
-  return (int)(len < cap ? len : cap);
-}
+// drop_idx (dropout counter) and varlen_len (clamped sequence length):
+// attn_common.h, shared with cls_attention.hip
 
 // Tile-packed (TP) instantiations: the VARLEN kernels over a tile plan (see
 // fa_tile_plan_kernel) instead of over (sequence, tile) pairs. The plan is

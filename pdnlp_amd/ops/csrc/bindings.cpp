@@ -129,6 +129,19 @@ torch::Tensor flash_attn_tilepack_infer(torch::Tensor qkv, torch::Tensor plan,
 torch::Tensor bias_dropout_residual_ln_infer(
     torch::Tensor y, torch::Tensor bias, torch::Tensor res, torch::Tensor lnw,
     torch::Tensor lnb, double eps);
+std::vector<torch::Tensor> cls_attn_fwd(torch::Tensor qkv,
+                                        torch::Tensor cu_seqlens,
+                                        long rows_out, long max_seqlen,
+                                        long nh, double scale, double p,
+                                        torch::Tensor seed_buf, long salt);
+torch::Tensor cls_attn_infer(torch::Tensor qkv, torch::Tensor cu_seqlens,
+                             long rows_out, long max_seqlen, long nh,
+                             double scale);
+torch::Tensor cls_attn_bwd(torch::Tensor dout, torch::Tensor qkv,
+                           torch::Tensor o, torch::Tensor lse,
+                           torch::Tensor cu_seqlens, long max_seqlen, long nh,
+                           double scale, double p, torch::Tensor seed_buf,
+                           long salt);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_fwd", &layernorm_fwd);
@@ -191,4 +204,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("qkv"), py::arg("plan"), py::arg("max_seqlen"), py::arg("nh"),
         py::arg("scale"), py::arg("out") = py::none());
   m.def("bias_dropout_residual_ln_infer", &bias_dropout_residual_ln_infer);
+  // one query row per sequence (cls_attention.hip)
+  m.def("cls_attn_fwd", &cls_attn_fwd);
+  m.def("cls_attn_infer", &cls_attn_infer);
+  m.def("cls_attn_bwd", &cls_attn_bwd);
 }

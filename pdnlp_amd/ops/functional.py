@@ -641,6 +641,84 @@ def attention_varlen(qkv: torch.Tensor, cu_seqlens: torch.Tensor,
     return torch.cat(outs, dim=0)
 
 
+class _ClsAttnFn(torch.autograd.Function):
+    """Attention of every sequence's first token over its own sequence, on
+    the packed QKV projection [T, 3H] (cls_attention.hip): one output row
+    per sequence, [rows_out, H]. Built like _FlashAttnVarlenFn: dropout
+    masks are recomputed in backward from the device seed + salt, and the
+    masks are those ``flash_attn_varlen_fwd`` gives these rows. dqkv comes
+    back in the packed layout: k and v columns of every sequence row, q
+    columns of the first rows, everything else exactly zero."""
+
+    @staticmethod
+    def forward(ctx, qkv, cu_seqlens, rows_out, max_seqlen, nh, scale,
+                p_drop):
+        if p_drop > 0.0:
+            seed_buf, salt = _dropout_seed.get(qkv.device)
+        else:
+            seed_buf, salt = torch.Tensor(), 0
+        o, lse = ext().cls_attn_fwd(qkv, cu_seqlens, rows_out, max_seqlen,
+                                    nh, scale, p_drop, seed_buf, salt)
+        ctx.save_for_backward(qkv, o, lse, cu_seqlens,
+                              seed_buf if p_drop > 0.0 else torch.Tensor())
+        ctx.max_seqlen = max_seqlen
+        ctx.nh, ctx.scale, ctx.p, ctx.salt = nh, scale, p_drop, salt
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, lse, cu_seqlens, seed_buf = ctx.saved_tensors
+        dqkv = ext().cls_attn_bwd(
+            do.contiguous(), qkv, o, lse, cu_seqlens, ctx.max_seqlen, ctx.nh,
+            ctx.scale, ctx.p, seed_buf, ctx.salt)
+        return dqkv, None, None, None, None, None, None
+
+
+def cls_attention(qkv: torch.Tensor, cu_seqlens: torch.Tensor, rows_out: int,
+                  max_seqlen: int, num_heads: int, dropout_p: float = 0.0,
+                  training: bool = False) -> torch.Tensor:
+    """First-token attention on a packed QKV projection output.
+
+    qkv: [T, 3H] and cu_seqlens int32 [B+1] as in :func:`attention_varlen`.
+    Returns [rows_out, H] with ``rows_out >= B``: row i < B is the attention
+    output of sequence i's first token over the keys of its own sequence;
+    rows of empty sequences and rows >= B are exactly zero. This is
+    ``attention_varlen(...)[cu_seqlens[:-1]]`` without the other T - B query
+    rows. Runs the one-wave-per-(sequence, head) HIP kernel wherever
+    :func:`attention_varlen` runs its fused kernel, and a torch composition
+    (which reads cu_seqlens on the host) otherwise."""
+    T, H3 = qkv.shape
+    H = H3 // 3
+    hd = H // num_heads
+    rows_out = int(rows_out)
+    p_eff = float(dropout_p if training else 0.0)
+    if hip_enabled(qkv) and hd == 64 and T % 64 == 0 \
+            and qkv.dtype in (torch.bfloat16, torch.float16):
+        scale = 1.0 / math.sqrt(hd)
+        if p_eff == 0.0 and _infer_active():
+            return ext().cls_attn_infer(
+                qkv.contiguous(), cu_seqlens.contiguous(), rows_out,
+                int(max_seqlen), num_heads, scale)
+        return _ClsAttnFn.apply(
+            qkv.contiguous(), cu_seqlens.contiguous(), rows_out,
+            int(max_seqlen), num_heads, scale, p_eff)
+    bounds = cu_seqlens.tolist()
+    if rows_out < len(bounds) - 1:
+        raise ValueError("cls_attention: rows_out must be at least the "
+                         "number of sequences")
+    outs = []
+    for s0, s1 in zip(bounds[:-1], bounds[1:]):
+        if s1 <= s0:
+            outs.append(qkv.new_zeros(1, H))
+            continue
+        q, k, v = (t.view(1, -1, num_heads, hd).transpose(1, 2)
+                   for t in qkv[s0:s1].split(H, dim=-1))
+        c = attention(q[:, :, :1], k, v, None, p_eff, training)
+        outs.append(c.transpose(1, 2).reshape(1, H))
+    outs.append(qkv.new_zeros(rows_out - (len(bounds) - 1), H))
+    return torch.cat(outs, dim=0)
+
+
 # --------------------------------------------------------------------------
 # Bias + dropout + residual + LayerNorm (K6/K8 epilogue)
 # --------------------------------------------------------------------------

@@ -46,7 +46,9 @@ def main():
                    help="graphed = hipGraph-captured serving forward "
                         "(pdnlp_amd.engine.InferenceEngine); packed = its "
                         "padding-free form (packed token stream, one graph "
-                        "per bucketed size, forward-only kernels)")
+                        "per bucketed size, forward-only kernels); with "
+                        "--cls-only-last-layer true its last encoder layer "
+                        "computes the first-token rows only")
     ns, rest = p.parse_known_args()
     args = Args().apply_cli(rest)
     set_seed(args.seed)
@@ -81,7 +83,8 @@ def main():
             if torch.cuda.is_available():
                 model = model.to(torch.bfloat16)
             eng = InferenceEngine(model, tokenizer, device=str(device),
-                                  max_seq_len=args.max_seq_len, packed=True)
+                                  max_seq_len=args.max_seq_len, packed=True,
+                                  cls_only_last_layer=args.cls_only_last_layer)
             pred = eng.predict([text])[0]
             print(f"{c or '<random-init>'} → predicted: {LABELS[pred]} "
                   f"(packed, {eng.graph_stats})")

@@ -12,7 +12,9 @@ one process and the per-round means are reported with their range. The plan
 kernel (once per model forward, not per layer) is timed on its own. The
 serving pair rides along: the tile-packed forward at p = 0 (zero-fill launch,
 kernel, lse) next to ``flash_attn_tilepack_infer``, which replaces it under
-``ops.inference_kernels()``.
+``ops.inference_kernels()``. The one-query-row-per-sequence kernels of the
+CLS-only last layer (``cls_attn_fwd`` / ``cls_attn_bwd`` / ``cls_attn_infer``,
+``ceil64(slots)`` output rows) are timed on the same batch.
 """
 import argparse
 import json
@@ -95,6 +97,10 @@ def packed(a):
     assert plan[0].item() == len(items)
     o_ps, lse_ps = e.flash_attn_varlen_fwd(qkv, cu_t, mx, nh, sc, p, seed, 1)
     o_tp, lse_tp = e.flash_attn_tilepack_fwd(qkv, plan, mx, nh, sc, p, seed, 1)
+    rows_out = (nseq + 63) // 64 * 64
+    do_cls = torch.randn(rows_out, H, device=dev).bfloat16()
+    o_cls, lse_cls = e.cls_attn_fwd(qkv, cu_t, rows_out, mx, nh, sc, p, seed,
+                                    1)
     fns = {
         "per_sequence_fwd": lambda: e.flash_attn_varlen_fwd(
             qkv, cu_t, mx, nh, sc, p, seed, 1),
@@ -109,6 +115,12 @@ def packed(a):
             qkv, plan, mx, nh, sc, 0.0, torch.Tensor(), 0),
         "tile_packed_infer": lambda: e.flash_attn_tilepack_infer(
             qkv, plan, mx, nh, sc),
+        "cls_fwd": lambda: e.cls_attn_fwd(
+            qkv, cu_t, rows_out, mx, nh, sc, p, seed, 1),
+        "cls_bwd": lambda: e.cls_attn_bwd(
+            do_cls, qkv, o_cls, lse_cls, cu_t, mx, nh, sc, p, seed, 1),
+        "cls_infer": lambda: e.cls_attn_infer(
+            qkv, cu_t, rows_out, mx, nh, sc),
     }
     for fn in fns.values():
         for _ in range(10):
@@ -129,6 +141,11 @@ def packed(a):
     print(f"serving fwd: ranges disjoint in favour of infer: "
           f"{max(inf) < min(f0)}; of the training forward: "
           f"{max(f0) < min(inf)}")
+    for d in ("fwd", "bwd"):
+        tp, cl = us[f"tile_packed_{d}"], us[f"cls_{d}"]
+        print(f"{d}: {rows_out} first-token rows (cls) against all {T} rows "
+              f"(tile-packed): ranges disjoint in favour of cls: "
+              f"{max(cl) < min(tp)}")
     print(json.dumps({"metric": "bench_attention_packed", "rows": T,
                       "dropout": p, "sentences": len(bl),
                       "live_blocks_per_head": {"per_sequence": live,

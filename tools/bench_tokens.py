@@ -3,6 +3,8 @@
 
     python tools/bench_tokens.py [--budgets 1024,2048,4096] [--pairs 5]
                                  [--steps 30] [--hip-graph true]
+                                 [--attn-tile-pack true]
+                                 [--cls-only-last-layer true]
 
 Eager bf16 BERT-base training steps (forward, backward, fused AdamW) on the
 packed stream: ``--unpad true`` at batch 32 (the baseline) against
@@ -23,6 +25,10 @@ an emptied allocator cache. Ranges that overlap are reported as such.
 With ``--attn-tile-pack true`` every budget also runs with tile-packed
 attention (``tokensN_tp``, same batches, same windows), next to the same
 build with the option off.
+
+With ``--cls-only-last-layer true`` every budget also runs with the CLS-only
+last encoder layer (``tokensN_cls``, or ``tokensN_tp_cls`` on top of
+``--attn-tile-pack true``), next to the same build with that option off.
 
 With ``--hip-graph true`` every mode also runs through the Trainer's
 hipGraph cache: graphs captured, the share of an epoch's steps that
@@ -125,6 +131,7 @@ def main():
     ap.add_argument("--mem-steps", type=int, default=200)
     ap.add_argument("--hip-graph", default="false")
     ap.add_argument("--attn-tile-pack", default="false")
+    ap.add_argument("--cls-only-last-layer", default="false")
     ap.add_argument("--seed", type=int, default=123)
     ap.add_argument("--data-path", default="./data/train.json")
     a = ap.parse_args()
@@ -133,6 +140,7 @@ def main():
     dev = torch.device("cuda:0")
     use_graph = a.hip_graph.lower() in ("1", "true", "yes")
     tile_pack = a.attn_tile_pack.lower() in ("1", "true", "yes")
+    cls_only = a.cls_only_last_layer.lower() in ("1", "true", "yes")
     budgets = [int(x) for x in a.budgets.split(",")]
     print(f"device: {torch.cuda.get_device_name(0)}")
 
@@ -172,16 +180,20 @@ def main():
               f"{share * 100:.1f} % of the first epoch's steps replayed")
         epochs[name] = [to_device(b, dev) for b in timed]
 
-    # (mode name, pool name, tile-packed attention)
-    runs = [(name, name, False) for name in epochs]
+    # (mode name, pool name, tile-packed attention, CLS-only last layer)
+    runs = [(name, name, False, False) for name in epochs]
     if tile_pack:
-        runs += [(name + "_tp", name, True) for name in epochs
+        runs += [(name + "_tp", name, True, False) for name in epochs
                  if name.startswith("tokens")]
-    modes = [Mode(name, epochs[ep], dev, tp) for name, ep, tp in runs]
+    if cls_only:   # on top of the tile-packed mode when that is on
+        tp_tag = "_tp" if tile_pack else ""
+        runs += [(name + tp_tag + "_cls", name, tile_pack, True)
+                 for name in epochs if name.startswith("tokens")]
+    modes = [Mode(name, epochs[ep], dev, tp, co) for name, ep, tp, co in runs]
     graph_modes = []
     if use_graph:
-        graph_modes = [GraphMode(name + "_graph", epochs[ep], dev, tp)
-                       for name, ep, tp in runs]
+        graph_modes = [GraphMode(name + "_graph", epochs[ep], dev, tp, co)
+                       for name, ep, tp, co in runs]
     for m in modes + graph_modes:            # every batch of the pool, once
         m.window(len(m.batches))
     for m in graph_modes:
@@ -207,7 +219,8 @@ def main():
 
     result = {}
     for name, v in times.items():
-        base = name.replace("_graph", "").replace("_tp", "")
+        base = name.replace("_graph", "").replace("_tp", "") \
+            .replace("_cls", "")
         sps = info[base]["sentences_per_step"]
         result[name] = {
             "ms_per_step": v, "range_ms": [min(v), max(v)],
@@ -222,13 +235,24 @@ def main():
                             "below" if hi < base[0] else "overlapping")
         print(f"{name} samples/s against unpad{a.batch}: {r['vs_baseline']}")
     for name, r in result.items():   # option on against off, same batches
-        if "_tp" in name:
+        if "_tp" in name and "_cls" not in name:
             lo, hi = r["range_ms"]
             off = result[name.replace("_tp", "")]["range_ms"]
             r["vs_option_off"] = ("faster" if hi < off[0] else
                                   "slower" if lo > off[1] else "overlapping")
             print(f"{name} ms/step {lo:.3f} .. {hi:.3f} against option off "
                   f"{off[0]:.3f} .. {off[1]:.3f}: {r['vs_option_off']}")
+
+    for name, r in result.items():   # CLS-only last layer on against off
+        if "_cls" in name:
+            lo, hi = r["range_ms"]
+            off = result[name.replace("_cls", "")]["range_ms"]
+            r["vs_cls_only_off"] = ("faster" if hi < off[0] else
+                                    "slower" if lo > off[1] else
+                                    "overlapping")
+            print(f"{name} ms/step {lo:.3f} .. {hi:.3f} against "
+                  f"cls-only off {off[0]:.3f} .. {off[1]:.3f}: "
+                  f"{r['vs_cls_only_off']}")
 
     # memory: one mode resident at a time would need a rebuild; report the
     # growth of memory_reserved over mem-steps from an emptied cache instead

@@ -82,13 +82,15 @@ def to_device(b, dev):
 
 
 class Mode:
-    def __init__(self, name, batches, dev, tile_pack=False):
+    def __init__(self, name, batches, dev, tile_pack=False, cls_only=False):
         set_seed(123)
         self.name = name
         self.model = build_model("bert-base").to(torch.bfloat16).to(dev)
         self.model.train()
         if tile_pack:  # --attn-tile-pack true
             self.model.cfg.attn_tile_pack = True
+        if cls_only:   # --cls-only-last-layer true
+            self.model.cfg.cls_only_last_layer = True
         self.opt = build_optimizer(self.model, lr=3e-5)
         self.batches = batches
         self.i = 0
@@ -130,11 +132,12 @@ class GraphMode(Mode):
     (``--unpad true --hip-graph true``): one captured graph per batch key,
     eager fused AdamW between replays."""
 
-    def __init__(self, name, batches, dev, tile_pack=False):
-        super().__init__(name, batches, dev, tile_pack)
+    def __init__(self, name, batches, dev, tile_pack=False, cls_only=False):
+        super().__init__(name, batches, dev, tile_pack, cls_only)
         args = Args()
         args.unpad = True
         args.attn_tile_pack = tile_pack
+        args.cls_only_last_layer = cls_only
         args.hip_graph = False      # until capture_all()
         args.max_seq_len = S
         self.trainer = Trainer(args, self.model, self.opt, dev)

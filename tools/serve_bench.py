@@ -3,11 +3,16 @@
 
     python tools/serve_bench.py            # padded engine at seq 128
     python tools/serve_bench.py --packed   # padded vs padding-free serving
+    python tools/serve_bench.py --packed --cls-only-last-layer
 
 ``--packed`` serves the same requests with three engines: the graphed padded
 engine (the baseline: every text of a request padded to the power-of-two
 bucket of the longest), the packed engine on the training kernels
 (``infer_kernels=False``) and the packed engine on the forward-only kernels.
+``--cls-only-last-layer`` adds a fourth, ``packed_cls``: the packed engine
+whose last encoder layer computes the first-token rows only, reported next
+to ``packed`` (at request size 1 the two run the same code: the fallback
+rule).
 Text lengths come from tools/bench_unpad.py's seeded stand-in (real lengths
 when ./data/train.json exists, else lognormal, mean ~20, cap 128); token ids
 are random. For request sizes 1, 8 and 64 every engine first serves all
@@ -98,6 +103,9 @@ def packed(a):
             model, tok, packed=True, infer_kernels=False, **kw),
         "packed": InferenceEngine(model, tok, packed=True, **kw),
     }
+    if a.cls_only_last_layer:
+        engines["packed_cls"] = InferenceEngine(
+            model, tok, packed=True, cls_only_last_layer=True, **kw)
     serve = {k: ((lambda r, e=e: _serve_padded(e, r)) if k == "padded"
                  else e.forward_sequences) for k, e in engines.items()}
     source, lens = lengths(max(a.offline, 64 * a.requests), 123,
@@ -127,6 +135,12 @@ def packed(a):
             print(f"  p50 of {k} against padded: disjointly lower "
                   f"{max(mine) < min(base)}, disjointly higher "
                   f"{min(mine) > max(base)}")
+        if "packed_cls" in res:
+            base = [w[0] for w in res["packed"]]
+            mine = [w[0] for w in res["packed_cls"]]
+            print(f"  p50 of packed_cls against packed: disjointly lower "
+                  f"{max(mine) < min(base)}, disjointly higher "
+                  f"{min(mine) > max(base)}")
     # offline: texts of the stand-in lengths through the tokenizer
     g = torch.Generator().manual_seed(9)
     texts = ["".join(chr(0x4e00 + c) for c in
@@ -153,6 +167,9 @@ def packed(a):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--packed", action="store_true")
+    ap.add_argument("--cls-only-last-layer", action="store_true",
+                    help="with --packed: also the packed engine with the "
+                         "CLS-only last encoder layer")
     ap.add_argument("--requests", type=int, default=60,
                     help="requests per size and window")
     ap.add_argument("--windows", type=int, default=5)

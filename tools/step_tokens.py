@@ -1,9 +1,9 @@
 #!/usr/bin/env python
 """A fixed number of eager token-budget training steps, for profilers.
 
-    rocprofv3 --kernel-trace --stats -d DIR -- \\
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- \\
         python tools/step_tokens.py --max-tokens 4096 --steps 25 \\
-        [--attn-tile-pack true]
+        [--attn-tile-pack true] [--cls-only-last-layer true]
     python tools/step_tokens.py --summarize DIR --steps 25 --title "..."
 
 bf16 BERT-base with fused AdamW on the ``--max-tokens`` batches of
@@ -50,6 +50,7 @@ def main():
     ap.add_argument("--steps", type=int, default=25)
     ap.add_argument("--pool", type=int, default=10)
     ap.add_argument("--attn-tile-pack", default="false")
+    ap.add_argument("--cls-only-last-layer", default="false")
     ap.add_argument("--seed", type=int, default=123)
     ap.add_argument("--data-path", default="./data/train.json")
     ap.add_argument("--summarize", metavar="DIR", default=None)
@@ -67,16 +68,17 @@ def main():
         sys.exit("step_tokens.py runs GPU steps: no GPU visible")
     dev = torch.device("cuda:0")
     tile_pack = a.attn_tile_pack.lower() in ("1", "true", "yes")
+    cls_only = a.cls_only_last_layer.lower() in ("1", "true", "yes")
     source, lens = lengths(9200, a.seed, a.data_path)
     samples = padded_samples(lens, a.seed)
     sampler = TokenBudgetBatchSampler(lens, a.max_tokens, seed=a.seed)
     pool = [to_device(pack_batch(take(samples, b), total_rows=a.max_tokens,
                                  seq_multiple=SEQ_MULTIPLE), dev)
             for b in sampler.batches[:-1][:a.pool]]
-    mode = Mode("tokens", pool, dev, tile_pack)
+    mode = Mode("tokens", pool, dev, tile_pack, cls_only)
     ms = mode.window(a.steps)
     print(f"{source}; --max-tokens {a.max_tokens}, attn_tile_pack "
-          f"{tile_pack}: {a.steps} steps, {ms:.3f} ms/step wall")
+          f"{tile_pack}, cls_only_last_layer {cls_only}: {a.steps} steps, {ms:.3f} ms/step wall")
 
 
 if __name__ == "__main__":
