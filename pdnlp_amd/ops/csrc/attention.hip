@@ -20,7 +20,9 @@
 //  - Backward: two atomics-free passes. dQ pass owns 64-row blocks; dK/dV
 //    pass owns 64-key blocks and computes S^T = K@Q^T so every GEMM is the
 //    native MFMA A@B^T form. Transposed B-operands (V^T, K^T, Q^T, dO^T)
-//    come from ds_read_b64_tr_b16 hardware transpose reads.
+//    come from ds_read_b64_tr_b16 hardware transpose reads. Sequences of
+//    at most 128 rows take ONE launch instead: fa_bwd_fused_kernel holds a
+//    whole head in LDS and computes every P and dS entry once.
 //
 // VARLEN instantiations run the same three kernels over a padding-free
 // token stream [T, 3H]: sequence b is rows cu_seqlens[b]..cu_seqlens[b+1],
@@ -43,6 +45,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include <cstdlib>
 #include <optional>
 
 #include "attn_common.h"  // drop_idx, varlen_len
@@ -867,6 +870,338 @@ void fa_bwd_dkv_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
 }
 
 // ---------------------------------------------------------------------------
+// backward, fused: sequences of at most 128 rows. One workgroup per (batch,
+// head) holds Q, K, V and dO of the whole head in LDS and computes every P
+// and dS entry once: S^T = K@Q^T per (key tile, query tile) pair as the dK/dV
+// kernel does, dV and dK from the wave's own 16 key rows of the P^T / dS^T
+// image, and dQ from the same dS^T image read transposed for the wave's own
+// 16 query rows. Dvec stays in LDS; nothing goes through global memory
+// between the parts. dK and dV accumulate in the dK/dV kernel's order, dQ
+// over the key tiles in the dQ kernel's order.
+// ---------------------------------------------------------------------------
+
+// dynamic-LDS carve (bytes, every offset a multiple of 16; no static LDS in
+// the kernel, so the dynamic base stays aligned): two tiles each of Q, K, V
+// and dO, one P^T / dS^T image, then the lse, Dvec and mask rows
+constexpr int FB_TILE = 64 * 128;
+constexpr int FB_Q = 0;
+constexpr int FB_K = 2 * FB_TILE;
+constexpr int FB_V = 4 * FB_TILE;
+constexpr int FB_DO = 6 * FB_TILE;
+constexpr int FB_PDS = 8 * FB_TILE;
+constexpr int FB_LSE = 9 * FB_TILE;
+constexpr int FB_DVEC = FB_LSE + 128 * 4;
+constexpr int FB_MASK = FB_DVEC + 128 * 4;
+constexpr int FB_LDS_BYTES = FB_MASK + 128 * 2;  // 75008: two per CU
+
+// two transposed fragments, as read_tr4
+template <typename V8>
+__device__ __forceinline__ void read_tr2(unsigned int b0, unsigned int b1,
+                                         V8* f) {
+  uint2v r0, r1, r2, r3;
+  asm volatile(
+      "ds_read_b64_tr_b16 %0, %4\n\t"
+      "ds_read_b64_tr_b16 %1, %4 offset:512\n\t"
+      "ds_read_b64_tr_b16 %2, %5\n\t"
+      "ds_read_b64_tr_b16 %3, %5 offset:512\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)
+      : "v"(b0), "v"(b1)
+      : "memory");
+  reinterpret_cast<uint2v*>(&f[0])[0] = r0;
+  reinterpret_cast<uint2v*>(&f[0])[1] = r1;
+  reinterpret_cast<uint2v*>(&f[1])[0] = r2;
+  reinterpret_cast<uint2v*>(&f[1])[1] = r3;
+}
+
+// two waves per SIMD (the second __launch_bounds__ argument): the register
+// budget that lets the two workgroups the LDS admits share a CU
+template <typename T, typename V8, bool HAS_MASK, bool DROP, bool VARLEN>
+__global__ __launch_bounds__(NTHREADS, 2)
+void fa_bwd_fused_kernel(const T* __restrict__ dout, const T* __restrict__ qkv,
+                         const T* __restrict__ o, const float* __restrict__ lse,
+                         const T* __restrict__ mask, T* __restrict__ dqkv,
+                         const unsigned long long* __restrict__ seed_base,
+                         unsigned long long salt, float scale, float p,
+                         int nh, int S, const int* __restrict__ cu_seqlens) {
+  extern __shared__ __attribute__((aligned(16))) char fb_lds[];
+  const float scale2 = scale * 1.4426950408889634f;  // exp2 domain
+  const int bh = blockIdx.x;
+  const long b = bh / nh, h = bh % nh;
+  const long H = (long)nh * 64, ld = 3 * H;
+  // sequence rows [row0, row0 + len), as in fa_fwd_kernel; the host sends
+  // max_seqlen <= 128 here, and a longer sequence of a bad cu_seqlens is cut
+  // to the 128 rows the LDS holds
+  const long row0 = VARLEN ? (long)cu_seqlens[b] : b * S;
+  int len = VARLEN ? varlen_len(cu_seqlens, b, row0, S) : S;
+  len = len < 128 ? len : 128;
+  if (VARLEN && len <= 0) return;  // block-uniform, before any barrier
+  const int nt = (len + 63) / 64;  // 1 or 2
+  const long stat0 = VARLEN ? h * S + row0 : (long)bh * S;  // lse row base
+  const T* qbase = qkv + row0 * ld + h * 64;
+  const T* kbase = qbase + H;
+  const T* vbase = qbase + 2 * H;
+  const T* dobase = dout + row0 * H + h * 64;
+  const T* obase = o + row0 * H + h * 64;
+  T* dqbase = dqkv + row0 * ld + h * 64;
+  T* dkbase = dqbase + H;
+  T* dvbase = dqbase + 2 * H;
+
+  char* q_lds = fb_lds + FB_Q;
+  char* k_lds = fb_lds + FB_K;
+  char* v_lds = fb_lds + FB_V;
+  char* do_lds = fb_lds + FB_DO;
+  char* pds_lds = fb_lds + FB_PDS;
+  float* lse_lds = reinterpret_cast<float*>(fb_lds + FB_LSE);
+  float* dvec_lds = reinterpret_cast<float*>(fb_lds + FB_DVEC);
+  T* mask_lds = reinterpret_cast<T*>(fb_lds + FB_MASK);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+  const int wid = tid >> 6;
+  const int wr = wid * 16;  // the wave's key rows (dK/dV) and query rows (dQ)
+  const unsigned long long seed = DROP ? (*seed_base + salt) : 0ull;
+  const unsigned int seed32 = (unsigned int)(seed ^ (seed >> 32));
+  const float inv_keep = DROP ? 1.f / (1.f - p) : 1.f;
+
+  // prologue: every global load of the kernel. The ordinary loads go out
+  // first (lse, mask, and O in the fragment layout read_n gives dO in: lane
+  // l holds O[wr + (l&15)][ks*32 + (l>>4)*8 + i], rows clamped as staging
+  // clamps them), then the tiles by global_load_lds: one round trip.
+  float lse_v = 0.f;
+  if (tid < len) lse_v = lse[stat0 + tid];  // tail rows have no lse: not read
+  T mask_v = from_f32<T>(0.f);
+  if (HAS_MASK && tid < S) mask_v = mask[b * S + tid];
+  V8 ov[2][2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    if (t < nt) {
+      long r = t * 64 + wr + (lane & 15);
+      r = r < len ? r : len - 1;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+        ov[t][ks] = *reinterpret_cast<const V8*>(obase + r * H + ks * 32 +
+                                                 (lane >> 4) * 8);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    if (t < nt) {
+      stage64<T>(dobase, H, t * 64, len, do_lds + t * FB_TILE);
+      stage64<T>(qbase, ld, t * 64, len, q_lds + t * FB_TILE);
+      stage64<T>(kbase, ld, t * 64, len, k_lds + t * FB_TILE);
+      stage64<T>(vbase, ld, t * 64, len, v_lds + t * FB_TILE);
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (tid < 128) {
+    lse_lds[tid] = lse_v;
+    if (HAS_MASK) mask_lds[tid] = mask_v;
+  }
+  __syncthreads();
+
+  // Dvec = rowsum(dO * O): the dQ kernel's expression and add order; lane
+  // l&15 accumulates row wr+(l&15) over its quarter's 8 columns
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    if (t < nt) {
+      float acc = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        V8 dv = read_n<V8>(do_lds + t * FB_TILE, wr, ks);
+        V8 o8 = ov[t][ks];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          float a, bvv;
+          if constexpr (std::is_same<V8, bf16x8>::value) {
+            a = (float)((__bf16*)&dv)[i];
+            bvv = (float)((__bf16*)&o8)[i];
+          } else {
+            a = (float)((_Float16*)&dv)[i];
+            bvv = (float)((_Float16*)&o8)[i];
+          }
+          acc += a * bvv;
+        }
+      }
+      acc += __shfl_xor(acc, 16, WAVE);
+      acc += __shfl_xor(acc, 32, WAVE);
+      if ((lane >> 4) == 0) dvec_lds[t * 64 + wr + (lane & 15)] = acc;
+    }
+  }
+  __syncthreads();
+
+  f32x4 acc_dq[2][4] = {};
+  for (int kb = 0; kb < nt; ++kb) {
+    const char* kt_lds = k_lds + kb * FB_TILE;
+    const char* vt_lds = v_lds + kb * FB_TILE;
+    float mv[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      mv[r] = HAS_MASK
+                  ? to_f32<T>(mask_lds[kb * 64 + wr + (lane >> 4) * 4 + r]) *
+                        1.4426950408889634f
+                  : 0.f;
+    f32x4 acc_dk[4] = {}, acc_dv[4] = {};
+    for (int t = 0; t < nt; ++t) {
+      {
+        const char* qt_lds = q_lds + t * FB_TILE;
+        const char* dot_lds = do_lds + t * FB_TILE;
+        // S^T = K @ Q^T and dP^T = V @ dO^T on this (key, query) tile pair
+        f32x4 acc_st[4] = {}, acc_dpt[4] = {};
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          V8 ak = read_n<V8>(kt_lds, wr, ks);
+          V8 av = read_n<V8>(vt_lds, wr, ks);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            acc_st[j] =
+                mfma16<V8>(ak, read_n<V8>(qt_lds, j * 16, ks), acc_st[j]);
+            acc_dpt[j] =
+                mfma16<V8>(av, read_n<V8>(dot_lds, j * 16, ks), acc_dpt[j]);
+          }
+        }
+        float pt[4][4];
+        bool live[4][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int qrow = t * 64 + j * 16 + (lane & 15);
+          const float lse_j = lse_lds[qrow];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int gkey = kb * 64 + wr + (lane >> 4) * 4 + r;
+            pt[j][r] = exp2f(acc_st[j][r] * scale2 + mv[r] - lse_j);
+            // tail query rows have no lse: their P^T is 0 by index, never
+            // by arithmetic on that slot
+            if (VARLEN && qrow >= len) pt[j][r] = 0.f;
+            live[j][r] = true;
+            if (DROP) {
+              const unsigned int grow =
+                  VARLEN ? (unsigned int)(stat0 + qrow)
+                         : (unsigned int)bh * S + (unsigned int)qrow;
+              const unsigned int rr = hash_rng32(
+                  seed32, drop_idx<VARLEN>(grow, (unsigned int)gkey, S));
+              live[j][r] = (rr * 2.3283064365386963e-10f) >= p;
+            }
+          }
+        }
+        // the image is free once every wave has read the previous pair's
+        // dS^T for its dQ
+        __syncthreads();
+        // Pd^T tile -> LDS; dV += Pd^T @ dO
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int prow = wr + (lane >> 4) * 4 + r;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int qcol = j * 16 + (lane & 15);
+            const float pv = live[j][r] ? pt[j][r] * inv_keep : 0.f;
+            *reinterpret_cast<unsigned short*>(
+                pds_lds + tr_addr(prow, qcol)) =
+                f32_bits16<T>(pv);
+          }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          V8 a = read_n<V8>(pds_lds, wr, ks);
+          V8 bd[4];
+          read_tr4<V8>(tr_base(dot_lds, 0, ks * 32),
+                       tr_base(dot_lds, 16, ks * 32),
+                       tr_base(dot_lds, 32, ks * 32),
+                       tr_base(dot_lds, 48, ks * 32), bd);
+#pragma unroll
+          for (int jd = 0; jd < 4; ++jd)
+            acc_dv[jd] = mfma16<V8>(a, bd[jd], acc_dv[jd]);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // dS^T tile -> LDS (same buffer); dK += dS^T @ Q
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int prow = wr + (lane >> 4) * 4 + r;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int qrow = t * 64 + j * 16 + (lane & 15);
+            const float dvec_j = dvec_lds[qrow];
+            const float dpt = live[j][r] ? acc_dpt[j][r] * inv_keep : 0.f;
+            float dsv = pt[j][r] * (dpt - dvec_j) * scale;
+            // tail query rows and, for dQ, tail keys: dS is 0 by index (the
+            // values there come from clamped copies, not from data)
+            if (VARLEN && (qrow >= len || kb * 64 + prow >= len)) dsv = 0.f;
+            const int qcol = j * 16 + (lane & 15);
+            *reinterpret_cast<unsigned short*>(
+                pds_lds + tr_addr(prow, qcol)) =
+                f32_bits16<T>(dsv);
+          }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          V8 a = read_n<V8>(pds_lds, wr, ks);
+          V8 bq[4];
+          read_tr4<V8>(tr_base(qt_lds, 0, ks * 32),
+                       tr_base(qt_lds, 16, ks * 32),
+                       tr_base(qt_lds, 32, ks * 32),
+                       tr_base(qt_lds, 48, ks * 32), bq);
+#pragma unroll
+          for (int jd = 0; jd < 4; ++jd)
+            acc_dk[jd] = mfma16<V8>(a, bq[jd], acc_dk[jd]);
+        }
+        // every wave's 16 key rows of dS^T are in the image
+        __syncthreads();
+        // dQ += dS @ K: the image holds dS^T [key][query], so the wave's 16
+        // query rows are an entity-along-c fragment (hardware transpose)
+        V8 ads[2];
+        read_tr2<V8>(tr_base(pds_lds, wr, 0), tr_base(pds_lds, wr, 32), ads);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          V8 bk[4];
+          read_tr4<V8>(tr_base(kt_lds, 0, ks * 32),
+                       tr_base(kt_lds, 16, ks * 32),
+                       tr_base(kt_lds, 32, ks * 32),
+                       tr_base(kt_lds, 48, ks * 32), bk);
+          // t is block-uniform: static indices keep acc_dq in registers
+          if (t == 0) {
+#pragma unroll
+            for (int jd = 0; jd < 4; ++jd)
+              acc_dq[0][jd] = mfma16<V8>(ads[ks], bk[jd], acc_dq[0][jd]);
+          } else {
+#pragma unroll
+            for (int jd = 0; jd < 4; ++jd)
+              acc_dq[1][jd] = mfma16<V8>(ads[ks], bk[jd], acc_dq[1][jd]);
+          }
+        }
+      }
+    }
+    const int ccol = lane & 15;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const long gkey = kb * 64 + wr + (lane >> 4) * 4 + r;
+      if (VARLEN && gkey >= len) continue;  // tail keys are never stored
+#pragma unroll
+      for (int jd = 0; jd < 4; ++jd) {
+        dkbase[gkey * ld + jd * 16 + ccol] = from_f32<T>(acc_dk[jd][r]);
+        dvbase[gkey * ld + jd * 16 + ccol] = from_f32<T>(acc_dv[jd][r]);
+      }
+    }
+  }
+
+  const int ccol = lane & 15;
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    if (t < nt) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const long grow = t * 64 + wr + (lane >> 4) * 4 + r;
+        if (VARLEN && grow >= len) continue;  // tail rows are never stored
+#pragma unroll
+        for (int jd = 0; jd < 4; ++jd)
+          dqbase[grow * ld + jd * 16 + ccol] = from_f32<T>(acc_dq[t][jd][r]);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // tile plan of the TP instantiations: one workgroup, once per model forward
 // ---------------------------------------------------------------------------
 
@@ -1032,12 +1367,38 @@ static void fa_fwd_launch(const torch::Tensor& qkv, const torch::Tensor& mask,
   });
 }
 
-// Dvec = rowsum(dO*O) is computed inside the dQ pass (it already stages dO;
-// O goes through the dS buffer) and consumed by dK/dV
+// Sequences of at most 128 rows (not tile-packed) take fa_bwd_fused_kernel.
+// PDNLP_FA_BWD_SPLIT (read per call) keeps the two-kernel backward for them:
+// the A/B baseline and the reference of tests/test_attn_bwd_fused_gpu.py.
+template <bool TP>
+static bool fa_bwd_fused(long seq_max) {
+  return !TP && seq_max <= 128 && getenv("PDNLP_FA_BWD_SPLIT") == nullptr;
+}
+
+// the fused kernel's LDS is past the 64 KB a launch gets by default: raise
+// the instantiation's limit, once per device
+template <auto Kernel>
+static void fa_raise_dynamic_lds(int bytes) {
+  constexpr int MAX_DEV = 64;
+  static bool raised[MAX_DEV] = {};
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  if (dev >= 0 && dev < MAX_DEV && raised[dev]) return;
+  HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                bytes));
+  if (dev >= 0 && dev < MAX_DEV) raised[dev] = true;
+}
+
+// Split path: Dvec = rowsum(dO*O) is computed inside the dQ pass (it already
+// stages dO; O goes through the dS buffer) and consumed by dK/dV through
+// `dvec`. Fused path (`fused`, from fa_bwd_fused): one launch, `dvec` unused
+// and undefined.
 template <bool VARLEN, bool TP = false>
 static void fa_bwd_launch(const torch::Tensor& dout, const torch::Tensor& qkv,
                           const torch::Tensor& o, const torch::Tensor& lse,
                           const torch::Tensor& mask, torch::Tensor& dvec,
+                          bool fused,
                           torch::Tensor& dqkv, const int* cu_seqlens,
                           long seq_max, long batch, long S, long nh,
                           double scale, double p,
@@ -1046,6 +1407,23 @@ static void fa_bwd_launch(const torch::Tensor& dout, const torch::Tensor& qkv,
   FaLaunch L = fa_launch_setup(mask, seq_max, batch * nh, p, seed_buf);
   if (TP) L.grid = dim3(tp_items, nh);
   FA_DISPATCH(qkv.scalar_type(), L, VARLEN, [&] {
+    if constexpr (!TP && PRELOAD) {
+      if (fused) {
+        constexpr auto kernel =
+            fa_bwd_fused_kernel<scalar_t, V8, HAS_MASK, DROP, VARLEN>;
+        fa_raise_dynamic_lds<kernel>(FB_LDS_BYTES);
+        hipLaunchKernelGGL(
+            kernel, dim3(batch * nh), dim3(NTHREADS), FB_LDS_BYTES, L.stream,
+            (const scalar_t*)dout.data_ptr(), (const scalar_t*)qkv.data_ptr(),
+            (const scalar_t*)o.data_ptr(), (const float*)lse.data_ptr(),
+            HAS_MASK ? (const scalar_t*)mask.data_ptr() : nullptr,
+            (scalar_t*)dqkv.data_ptr(), L.seed, (unsigned long long)salt,
+            (float)scale, (float)p, (int)nh, (int)S, cu_seqlens);
+        return;
+      }
+    }
+    TORCH_CHECK(!fused && dvec.defined(),
+                "flash_attn: the two-kernel backward needs dvec");
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(
           kernel, L.grid, dim3(NTHREADS), 0, L.stream,
@@ -1082,9 +1460,12 @@ torch::Tensor flash_attn_qkv_bwd(torch::Tensor dout, torch::Tensor qkv,
   check_fa_args(qkv, mask, nh);
   const long B = qkv.size(0), S = qkv.size(1);
   auto dqkv = torch::empty_like(qkv);
-  auto dvec = torch::empty({B * nh, S}, qkv.options().dtype(torch::kFloat));
-  fa_bwd_launch<false>(dout, qkv, o, lse, mask, dvec, dqkv, nullptr, S, B, S,
-                       nh, scale, p, seed_buf, salt);
+  const bool fused = fa_bwd_fused<false>(S);
+  torch::Tensor dvec;  // global Dvec row: the two-kernel path only
+  if (!fused)
+    dvec = torch::empty({B * nh, S}, qkv.options().dtype(torch::kFloat));
+  fa_bwd_launch<false>(dout, qkv, o, lse, mask, dvec, fused, dqkv, nullptr, S,
+                       B, S, nh, scale, p, seed_buf, salt);
   return dqkv;
 }
 
@@ -1156,8 +1537,10 @@ torch::Tensor flash_attn_varlen_bwd(torch::Tensor dout, torch::Tensor qkv,
                   lse.is_contiguous() && lse.numel() == nh * S,
               "flash_attn_varlen: o [T, H] / lse [nh, T] from the forward");
   auto dqkv = torch::zeros_like(qkv);  // see flash_attn_varlen_fwd
-  auto dvec = torch::empty({nh, S}, qkv.options().dtype(torch::kFloat));
-  fa_bwd_launch<true>(dout, qkv, o, lse, torch::Tensor(), dvec, dqkv,
+  const bool fused = fa_bwd_fused<false>(max_seqlen);
+  torch::Tensor dvec;  // global Dvec row: the two-kernel path only
+  if (!fused) dvec = torch::empty({nh, S}, qkv.options().dtype(torch::kFloat));
+  fa_bwd_launch<true>(dout, qkv, o, lse, torch::Tensor(), dvec, fused, dqkv,
                       (const int*)cu_seqlens.data_ptr(), max_seqlen, B, S, nh,
                       scale, p, seed_buf, salt);
   return dqkv;
@@ -1256,9 +1639,9 @@ torch::Tensor flash_attn_tilepack_bwd(torch::Tensor dout, torch::Tensor qkv,
               "flash_attn_tilepack: o [T, H] / lse [nh, T] from the forward");
   auto dqkv = torch::zeros_like(qkv);  // see flash_attn_varlen_fwd
   auto dvec = torch::empty({nh, S}, qkv.options().dtype(torch::kFloat));
-  fa_bwd_launch<true, true>(dout, qkv, o, lse, torch::Tensor(), dvec, dqkv,
-                            (const int*)plan.data_ptr(), max_seqlen, 1, S, nh,
-                            scale, p, seed_buf, salt, M);
+  fa_bwd_launch<true, true>(dout, qkv, o, lse, torch::Tensor(), dvec, false,
+                            dqkv, (const int*)plan.data_ptr(), max_seqlen, 1,
+                            S, nh, scale, p, seed_buf, salt, M);
   return dqkv;
 }
 

@@ -2,6 +2,7 @@
 
     python tools/bench_attention.py            # padded kernels, wall clock
     python tools/bench_attention.py --packed   # per-sequence vs tile-packed
+    python tools/bench_attention.py --bwd      # fused vs two-kernel backward
 
 ``--packed`` times the per-sequence (VARLEN) and the tile-packed kernels,
 forward and backward, on one stand-in token-budget batch of ``--rows``
@@ -15,6 +16,12 @@ kernel, lse) next to ``flash_attn_tilepack_infer``, which replaces it under
 ``ops.inference_kernels()``. The one-query-row-per-sequence kernels of the
 CLS-only last layer (``cls_attn_fwd`` / ``cls_attn_bwd`` / ``cls_attn_infer``,
 ``ceil64(slots)`` output rows) are timed on the same batch.
+
+``--bwd`` times the padded backward at (32, 12, 128) and (32, 12, 64), bf16,
+p = 0.1, with an additive mask: the fused kernel (one launch) against the
+two-kernel path that ``PDNLP_FA_BWD_SPLIT`` keeps, the switch set around the
+timed launches, both alternating in one process, device events around
+``--iters`` launches, per-round means with their range over ``--rounds``.
 """
 import argparse
 import json
@@ -62,6 +69,55 @@ def event_us(fn, iters):
     t1.record()
     torch.cuda.synchronize()
     return t0.elapsed_time(t1) * 1e3 / iters
+
+
+SPLIT_SWITCH = "PDNLP_FA_BWD_SPLIT"
+
+
+def bwd(a):
+    e = ext()
+    torch.manual_seed(0)
+    p, sc = 0.1, 0.125
+    seed = torch.tensor([1234], dtype=torch.int64, device=dev)
+    shapes = {}
+    for (B, nh, S) in [(32, 12, 128), (32, 12, 64)]:
+        H = nh * 64
+        qkv = torch.randn(B, S, 3 * H, device=dev).bfloat16()
+        do = torch.randn(B, S, H, device=dev).bfloat16()
+        # padded tails of 0 .. S/2 keys, as a collated batch has them
+        tails = torch.randint(0, S // 2 + 1, (B, 1), device=dev)
+        mask = ((torch.arange(S, device=dev)[None] >= S - tails)
+                .to(torch.bfloat16) * -10000.0).contiguous()
+        o, lse = e.flash_attn_qkv_fwd(qkv, mask, nh, sc, p, seed, 1)
+
+        def call():
+            return e.flash_attn_qkv_bwd(do, qkv, o, lse, mask, nh, sc, p,
+                                        seed, 1)
+
+        def timed(split, iters):
+            assert SPLIT_SWITCH not in os.environ
+            if split:
+                os.environ[SPLIT_SWITCH] = "1"
+            try:
+                return event_us(call, iters)
+            finally:
+                os.environ.pop(SPLIT_SWITCH, None)
+
+        for split in (False, True):
+            timed(split, 10)
+        us = {"fused": [], "split": []}
+        for _ in range(a.rounds):
+            us["fused"].append(timed(False, a.iters))
+            us["split"].append(timed(True, a.iters))
+        f, s2 = us["fused"], us["split"]
+        print(f"B{B} nh{nh} S{S} bwd: fused {min(f):.1f} .. {max(f):.1f} us, "
+              f"split {min(s2):.1f} .. {max(s2):.1f} us over {a.rounds} "
+              f"rounds of {a.iters} launches (each with its output "
+              f"allocation); ranges disjoint in favour of fused: "
+              f"{max(f) < min(s2)}; of split: {max(s2) < min(f)}")
+        shapes[f"{B}x{nh}x{S}"] = us
+    print(json.dumps({"metric": "bench_attention_bwd_fused", "dropout": p,
+                      "dtype": "bf16", "us": shapes}))
 
 
 def packed(a):
@@ -156,6 +212,7 @@ def packed(a):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--packed", action="store_true")
+    ap.add_argument("--bwd", action="store_true")
     ap.add_argument("--rows", type=int, default=4096)
     ap.add_argument("--batch-index", type=int, default=0)
     ap.add_argument("--dropout", type=float, default=0.1)
@@ -164,4 +221,9 @@ if __name__ == "__main__":
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_attention.py measures GPU kernels: no GPU visible")
-    packed(args) if args.packed else padded()
+    if args.bwd:
+        bwd(args)
+    elif args.packed:
+        packed(args)
+    else:
+        padded()
